@@ -1,18 +1,26 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the decaf377 hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the headline workload over one batch of synthetic input that is
 already resident in HBM: BASELINE.json configs[3], 2^22 variable-base scalar multiplications
 (random Element x random Fr: decompress, [k]P, compress).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, runs W untimed and K timed steps, writes the last step's outputs if asked, and prints the
+headline line (value, ms_per_step, and the roofline views derived from the timed steps' own kernel times).
+  --dump-outputs DIR  rank 0 writes what its last timed step returned as DIR/encodings.npy ([m, 32] output bytes)
+                      and DIR/status.npy ([m] statuses), float32; m = all records up to 2^18, beyond that a fixed
+                      seeded sample of 2^18 record indices (sorted), the same for every run with the same arguments
+  --full              everything else, as below: the oracle's parity sample of every rank, the multi-GPU sub-jobs,
+                      the `extra` operations and sizes, and the CPU baseline
 
   --scaling weak      (default) 2^22 elements PER GPU: every rank owns its own shard, no data-path collective
   --scaling strong    configs[3] as written: 2^22 elements IN TOTAL, rank g owns n/G of them
   --from-root         (with either total) the batch lives on rank 0: every step scatters the inputs over
                       RCCL, runs the shards, gathers the outputs back; `collective_ms` reports their share
 
-Besides the contract keys the line carries
+Besides the contract keys the line carries (parity_sample_ok, cpu_baseline and extra with --full only)
   roofline       HBM view of the dominant kernel (k_scalar_mul_var): algorithmic bytes / launch
                  duration (HIP events on the launch stream) against the 8 TB/s peak;
   roofline_valu  the view that actually binds: integer MACs/s against the v_mad_u64_u32 issue
@@ -93,15 +101,22 @@ def parse():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     ap.add_argument("--from-root", action="store_true",
                     help="the batch starts and ends on rank 0: scatter -> shards -> gather inside the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32, at most 2^18 records")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity sample against the oracle, the multi-GPU sub-jobs, the extras and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: leave out the extras and the multi-GPU sub-jobs")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for plumbing tests)")
     ap.add_argument("--launch-check", action="store_true",
                     help="plumbing test of the self-launcher: ranks rendezvous over gloo on the CPU, rank 0 prints "
                          "{launch_check, ranks_seen}, nothing touches a GPU")
     ap.add_argument("--same-device", action="store_true",
                     help="plumbing test: every rank uses GPU 0 (needs --backend gloo; not a measurement)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch(args):
@@ -177,6 +192,36 @@ def usable_cores():
     return max(1, min(c, 256))
 
 
+def headline_inputs(torch, ctx, dev, count, rk):
+    """The headline's synthetic records of rank `rk`: (Encodings [count, 32], scalars [count, 32]) on `dev`, the same
+    for every run."""
+    g = torch.Generator(device=dev).manual_seed(666 + rk)
+    r0_ = torch.randint(0, 256, (count, 32), dtype=torch.uint8, device=dev, generator=g)
+    k_ = torch.randint(0, 256, (count, 32), dtype=torch.uint8, device=dev, generator=g)
+    return ctx.encode_to_curve(r0_), k_      # valid encodings, strategy of tests/operations.rs:6-11
+
+
+DUMP_MAX_RECORDS = 1 << 18                   # 2^18 x 33 float32 values = 33 MiB
+DUMP_SEED = 377
+
+
+def dump_rows(n):
+    """Record indices --dump-outputs writes: all of them up to DUMP_MAX_RECORDS, else a fixed seeded sample (sorted)."""
+    import numpy as np
+    if n <= DUMP_MAX_RECORDS:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_RECORDS, replace=False)).astype(np.int64)
+
+
+def dump_outputs(torch, out_dir, encodings, status):
+    """--dump-outputs: the last timed step's outputs as DIR/encodings.npy [m, 32] and DIR/status.npy [m], float32."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sel = torch.from_numpy(dump_rows(int(encodings.shape[0]))).to(encodings.device)
+    np.save(os.path.join(out_dir, "encodings.npy"), encodings[sel].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "status.npy"), status[sel].cpu().numpy().astype(np.float32))
+
+
 def time_op(torch, fn, steps, warmup):
     """Returns (avg kernel ms via HIP events on the current stream, wall ms per step).  The extras that last milliseconds or
     less are given 5-10 untimed calls: after a stretch of small kernels the clock needs that long to come back up."""
@@ -199,7 +244,8 @@ def main():
     args = parse()
     # The checker's libraries are built BEFORE anything opens the GPU (and before the ranks exist when this process is
     # the launcher): later on Oracle(build=False) only loads them -- no rank starts a program once it holds a GPU.
-    if not args.launch_check:
+    # A plain run uses no checker.
+    if args.full and not args.launch_check:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         from _oracle import prebuild
         prebuild(native=not args.no_cpu_baseline and int(os.environ.get("RANK", "0")) == 0)
@@ -259,10 +305,7 @@ def main():
 
     # synthetic records, generated on the device and resident before timing
     def make_inputs(count, rk):
-        g = torch.Generator(device=dev).manual_seed(666 + rk)
-        r0_ = torch.randint(0, 256, (count, 32), dtype=torch.uint8, device=dev, generator=g)
-        k_ = torch.randint(0, 256, (count, 32), dtype=torch.uint8, device=dev, generator=g)
-        return ctx.encode_to_curve(r0_), k_      # valid encodings, strategy of tests/operations.rs:6-11
+        return headline_inputs(torch, ctx, dev, count, rk)
 
     kernel_events = []                           # every launch of compute(), in order (the sub-jobs below slice it)
     last_local = []                              # this rank's last launch: inputs and outputs (parity sample below)
@@ -289,11 +332,15 @@ def main():
     out, status = res["outputs"] if rank == 0 else (None, None)
     if rank == 0 and out is not None:
         assert int(status.sum().item()) == 0, "valid inputs must all decode"
-    # Every rank checks a sample of ITS OWN last launch against the oracle (the checker; after the timed region):
-    # 256 records spread evenly over the shard.  MIN over ranks, so one wrong rank fails the line.
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from _oracle import Oracle
-    checker = Oracle(build=False)
+        if args.dump_outputs:
+            dump_outputs(torch, args.dump_outputs, out, status)
+    # With --full every rank checks a sample of ITS OWN last launch against the oracle (the checker; after the timed
+    # region): 256 records spread evenly over the shard.  MIN over ranks, so one wrong rank fails the line.
+    checker = None
+    if args.full:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from _oracle import Oracle
+        checker = Oracle(build=False)
 
     def parity_of_last_launch():
         """(ok, records checked): 256 records spread over this rank's last launch against the oracle; MIN over ranks."""
@@ -320,14 +367,15 @@ def main():
         dist.all_gather(bufs, mine)
         return [float(b.item()) for b in bufs]
 
-    parity_ok, parity_cnt = parity_of_last_launch()
+    parity_ok, parity_cnt = parity_of_last_launch() if args.full else (1, 0)
     head_local = list(last_local)                # the headline's last launch on this rank (the cpu_baseline leg compares against it)
     ranks_seen = dist.get_world_size() if dist.is_initialized() else 1
-    # the extra ops and the CPU baseline below reuse rank 0's records
-    g = torch.Generator(device=dev).manual_seed(666 + rank)
-    r0 = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device=dev, generator=g)
-    scalars = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device=dev, generator=g)
-    points = ctx.encode_to_curve(r0)
+    if args.full:
+        # the extra ops and the CPU baseline below reuse rank 0's records
+        g = torch.Generator(device=dev).manual_seed(666 + rank)
+        r0 = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device=dev, generator=g)
+        scalars = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device=dev, generator=g)
+        points = ctx.encode_to_curve(r0)
 
     value = res["units"] / elapsed
     line = {
@@ -357,8 +405,9 @@ def main():
     }
     line["ranks_seen"] = ranks_seen              # size of the process group the timed region ran in
     line["backend"] = (args.backend + (" (RCCL)" if args.backend == "nccl" else "")) if dist.is_initialized() else "none (one process)"
-    line["parity_sample_ok"] = bool(parity_ok)   # every rank: >= parity_sample_per_rank outputs of its last launch == oracle
-    line["parity_sample_per_rank"] = parity_cnt
+    if args.full:
+        line["parity_sample_ok"] = bool(parity_ok)   # every rank: >= parity_sample_per_rank outputs of its last launch == oracle
+        line["parity_sample_per_rank"] = parity_cnt
     if args.from_root:
         line["collective_ms"] = res["collective_s"] * 1e3 / args.steps
     n = max(n_launch, 1) if mode != "weak" else n
@@ -427,7 +476,7 @@ def main():
     # 2^22 pairs IN TOTAL sharded over the GPUs, with the scatter / gather over RCCL when the batch lives on one of them,
     # and configs[4] is the Elligator batch at 2^20 in total: measured here with the same barrier + MAX-over-ranks rule.
     multi = {}
-    if world > 1 and not args.no_extra and mode == "weak":
+    if world > 1 and args.full and not args.no_extra and mode == "weak":
         sub_steps = max(1, min(args.steps, 10))
         for key, sub_mode in (("strong_2^%d_total" % args.log2n, "strong"), ("from_root", "from-root")):
             first_event = len(kernel_events)
@@ -470,7 +519,7 @@ def main():
                                                "note": "BASELINE configs[4]: contiguous shards, slowest rank's kernel time"}
         line["parity_sample_ok"] = bool(parity_ok)
 
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         extra = dict(multi)
         ne = min(1 << 20, n)
         # from 2 elements per resident lane (2 workgroups x 256 lanes per CU) decompress / compress / round trip run in chunks with
@@ -623,7 +672,7 @@ def main():
 
     # The CPU leg runs on rank 0 at every N (the other ranks wait at the barrier below): the same host cores, the same run.
     cpu_leg_error = None
-    if rank == 0 and not args.no_cpu_baseline and head_local and int(head_local[0].shape[0]) >= 4096:
+    if args.full and rank == 0 and not args.no_cpu_baseline and head_local and int(head_local[0].shape[0]) >= 4096:
         try:
             orc = Oracle(native=True, build=False)
             cores = usable_cores()

@@ -1835,12 +1835,12 @@ def test_bench_modes_and_rccl_single_rank():
 
 
 def test_bench_line_contract():
-    """The one JSON line of `python bench.py` (N = 1, small size so that the CPU baseline leg is short): every key of the
+    """The one JSON line of `python bench.py --full` (N = 1, small size so that the CPU baseline leg is short): every key of the
     driver's contract, the `roofline` and `cpu_baseline` objects, this round's `ranks_seen` / `parity_sample_ok`, and a
     `roofline_valu` for every extra that is one of BASELINE.json's configurations."""
     import json
     import subprocess
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--log2n", "16"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--log2n", "16", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1867,6 +1867,41 @@ def test_bench_line_contract():
     assert set(d_["extra"]["msm_mid_ms_per_call"]) == {"2^16"}
 
 
+def test_bench_plain_run_and_dumped_outputs(ctx, torch_mod, oracle, tmp_path):
+    """A plain `python bench.py` (no --full) times exactly --steps steps, prints the headline line without the legs --full
+    adds, and --dump-outputs writes what its last timed step returned: float32 arrays equal to the same launch made here on
+    the bench's own inputs, and to the oracle on a sample."""
+    import importlib.util
+    import json
+    import subprocess
+    torch = torch_mod
+    n = 1 << 16
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log2n", "16",
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d_ = json.loads(lines[0])
+    assert d_["steps"] == 3 and d_["warmup"] == 1 and d_["unit"] == "scalar-mults/s" and d_["higher_is_better"] is True
+    assert d_["dtype"] == "u32" and d_["ms_per_step"] > 0 and abs(d_["value"] - n * 3 / (d_["ms_per_step"] * 3e-3)) / d_["value"] < 1e-6
+    assert not {"extra", "cpu_baseline", "parity_sample_ok"} & set(d_), sorted(d_)
+    enc_d, st_d = np.load(tmp_path / "encodings.npy"), np.load(tmp_path / "status.npy")
+    assert sorted(os.listdir(tmp_path)) == ["encodings.npy", "status.npy"]
+    assert enc_d.dtype == np.float32 and enc_d.shape == (n, 32) and st_d.dtype == np.float32 and st_d.shape == (n,)
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert (b.dump_rows(n) == np.arange(n)).all()
+    dev = torch.device("cuda:0")
+    pts, ks = b.headline_inputs(torch, ctx, dev, n, 0)
+    o, st = ctx.scalar_mul_var(pts, ks)
+    assert (enc_d == o.cpu().numpy().astype(np.float32)).all() and (st_d == st.cpu().numpy().astype(np.float32)).all()
+    assert not st_d.any()
+    sel = np.linspace(0, n - 1, 64).round().astype(np.int64)
+    o_out, o_st = oracle.scalar_mul_var(pts.cpu().numpy()[sel], ks.cpu().numpy()[sel])
+    assert (enc_d[sel].astype(np.uint8) == o_out).all() and (st_d[sel] == o_st).all()
+
+
 def test_bench_self_launches_its_ranks():
     """`python bench.py --gpus 2` with NO launcher: the parent starts the two ranks itself before anything touches the
     GPU and relays rank 0's line.  Both ranks share GPU 0 and rendezvous over gloo (this box has one GPU); on a node
@@ -1875,7 +1910,7 @@ def test_bench_self_launches_its_ranks():
     import json
     import subprocess
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-device", "--backend", "gloo",
-                        "--steps", "2", "--warmup", "1", "--log2n", "16"],
+                        "--steps", "2", "--warmup", "1", "--log2n", "16", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -74,3 +74,23 @@ def test_bench_self_launch_propagates_failure():
                         "--no-cpu-baseline", "--no-extra"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_dump_sample_is_fixed():
+    """--dump-outputs beyond 2^18 records writes a fixed seeded sample: 2^18 distinct sorted indices inside the batch, the
+    same in every process, so that two builds' dumps compare record for record (at most 2^18 x 33 float32 = 33 MiB)."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    n = 1 << 22
+    rows = b.dump_rows(n)
+    assert rows.shape == (b.DUMP_MAX_RECORDS,) == (1 << 18,) and rows.dtype == np.int64
+    assert rows[0] >= 0 and rows[-1] < n and (np.diff(rows) > 0).all()
+    code = "import importlib.util, sys; s = importlib.util.spec_from_file_location('bench', sys.argv[1]); b = importlib.util.module_from_spec(s); " \
+           "s.loader.exec_module(b); r = b.dump_rows(1 << 22); print(int(r.sum()), int(r[:64].sum()), int(r[-64:].sum()))"
+    r = subprocess.run([sys.executable, "-c", code, os.path.join(ROOT, "bench.py")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.split() == [str(int(rows.sum())), str(int(rows[:64].sum())), str(int(rows[-64:].sum()))]
+    assert (b.dump_rows(1000) == np.arange(1000)).all() and b.DUMP_MAX_RECORDS * 33 * 4 <= 64 << 20

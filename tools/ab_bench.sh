@@ -3,7 +3,7 @@
 # usage: tools/ab_bench.sh [bench args]
 for lib in build/variants/*.so; do
   echo "== $lib"
-  D377_LIB=$PWD/$lib timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
+  D377_LIB=$PWD/$lib timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 for lib in "$ROOT"/build/variants/*.so; do
   v=$(basename "$lib" .so)
   export D377_LIB=$lib
-  timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$ROOT/$out/$v" -- python3 "$ROOT/bench.py" --steps 1 --warmup 0 --no-cpu-baseline > "$ROOT/$out/$v.log" 2>&1
+  timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$ROOT/$out/$v" -- python3 "$ROOT/bench.py" --full --steps 1 --warmup 0 --no-cpu-baseline > "$ROOT/$out/$v.log" 2>&1
 done
 cd "$ROOT"
 python3 - "$out" <<'P'

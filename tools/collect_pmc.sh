@@ -9,7 +9,7 @@ out=$1; shift
 mkdir -p "$out"
 ROOT=$(pwd)
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline $*"
+BENCH="python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline $*"
 timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$out/stats" -- $BENCH > "$ROOT/$out/bench_under_rocprof.log" 2>&1
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM SQ_INSTS_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES" \

@@ -11,7 +11,7 @@ it only starts the legs below as child processes and checks their exit codes.
                                     multi-device d377_msm -- all against the oracle / the single-device results
   leg 2  tests/dist_worker_gpu.py   G processes, one per GPU, backend nccl (= RCCL over xGMI): scatter of input records,
                                     gather of outputs, all-gather of MSM partial sums, MAX all-reduce of the timings
-  leg 3  bench.py --gpus G          the driver's command at a small size, self-launched; the line must report
+  leg 3  bench.py --gpus G --full   the driver's command at a small size, self-launched; the line must report
                                     ranks_seen == G and parity_sample_ok
 
 With one GPU visible: leg 1 lists GPU 0 twice, leg 2 runs one rank, leg 3 runs two ranks on GPU 0 over gloo."""
@@ -104,7 +104,7 @@ def main():
     print("leg 2 ok", flush=True)
 
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--log2n", str(args.log2n),
-           "--no-cpu-baseline", "--no-extra"]
+           "--full", "--no-cpu-baseline", "--no-extra"]
     cmd += ["--gpus", str(G)] if G > 1 else ["--gpus", "2", "--same-device", "--backend", "gloo"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -25,7 +25,7 @@ leg() {
 export PYTHONUNBUFFERED=1
 if [[ $part == *a* ]]; then
   leg 900 "$out/collect_pmc.log" bash tools/collect_pmc.sh "$out/pmc"
-  timeout -k 10 600 python3 -u bench.py > "$out/bench_line.json" 2> "$out/bench_line.err"
+  timeout -k 10 600 python3 -u bench.py --full > "$out/bench_line.json" 2> "$out/bench_line.err"
   [ -s "$out/bench_line.json" ] && grep -q '"roofline"' "$out/bench_line.json" || FAILED+=("bench_line.json")
   echo "bench: $(head -c 160 "$out/bench_line.json")"
   leg 700 "$out/size_sweep.txt" python3 -u tools/size_sweep.py
