@@ -13,6 +13,7 @@
 //   bytes are identical).
 #pragma once
 #include "fq29.hpp"
+#include "fqs29.hpp"
 
 namespace d377 {
 
@@ -422,7 +423,8 @@ D377_HD bool fq_addsub_words(const uint32_t a[8], const uint32_t b[8], bool sub,
 D377_HD fe fe_abs(const fe& a) { return fe_select(fe_is_negative(a), fe_neg(a), a); }
 
 // ---- group ----------------------------------------------------------------------------------
-struct ge { fe x, y, z, t; };   // extended twisted Edwards, a = -1, d = 3021; x*y = z*t
+template <class F> struct ge_of { F x, y, z, t; };   // extended twisted Edwards, a = -1, d = 3021; x*y = z*t
+using ge = ge_of<fe>;
 
 D377_HD ge ge_identity() {
   ge r;
@@ -558,6 +560,20 @@ D377_HD ge ge_select(bool c, const ge& a, const ge& b) {
   ge r;
   r.x = fe_select(c, a.x, b.x); r.y = fe_select(c, a.y, b.y);
   r.z = fe_select(c, a.z, b.z); r.t = fe_select(c, a.t, b.t);
+  return r;
+}
+
+// a point in the field type F of a templated chain, and back (fqs29.hpp: fe_as, fe_unsigned)
+template <class F>
+D377_HD ge_of<F> ge_as(const ge& p) {
+  ge_of<F> r;
+  r.x = fe_as<F>(p.x); r.y = fe_as<F>(p.y); r.z = fe_as<F>(p.z); r.t = fe_as<F>(p.t);
+  return r;
+}
+D377_HD const ge& ge_unsigned(const ge& p) { return p; }
+D377_HD ge ge_unsigned(const ge_of<fes>& p) {
+  ge r;
+  r.x = fe_unsigned(p.x); r.y = fe_unsigned(p.y); r.z = fe_unsigned(p.z); r.t = fe_unsigned(p.t);
   return r;
 }
 
@@ -866,7 +882,8 @@ D377_HD int fr_digit(const uint32_t digits[8], int i) {   // signed value of nib
 // kept in "cached" form (Y+X, Y-X, 2Z, 2d*T), and the doubling is sign-folded so it needs two
 // offset subtractions instead of four (with G' = A-B, H' = A+B, F' = G'+C, E' = H'-S:
 // X3 = E'F', Y3 = G'H', Z3 = F'G', T3 = E'H').
-struct gec { fe ypx, ymx, z2, kt; };      // cached extended point
+template <class F> struct gec_of { F ypx, ymx, z2, kt; };      // cached extended point
+using gec = gec_of<fe>;
 
 // ---- per-lane arithmetic of the four-lane group operations (quad_ops.hpp) -------------------------
 // Between its two rounds of products a lane of the quad forms ONE linear combination of the round-one products -- the
@@ -889,17 +906,20 @@ D377_HD fe gq_add_in_own(int role, const fe& u, const fe& v) {
 // addition, between the rounds: u - v or u + v.   role 0: E = b - a, 1: H = b + a, 2: F = d -+ c, 3: G = d +- c
 D377_HD fe gq_add_own(bool sub, const fe& u, const fe& v) { return fe_carry(fe_add(u, fe_select(sub, fe_neg_nc(v), v))); }
 
-
-
-D377_HD ge ge_double_fast(const ge& p, bool with_t) {
-  fe a = fe_sqr(p.x), b = fe_sqr(p.y);
-  fe c = fe_sqr2x(p.z);                   // 2 Z^2 for the price of Z^2
-  fe s_ = fe_sqr(fe_add(p.x, p.y));
-  fe h = fe_add(a, b);                    // H' lazy
-  fe e = fe_sub(h, s_);                   // E' = A + B - (X+Y)^2, carried
-  fe g = fe_sub(a, b);                    // G' carried
-  fe f = fe_add(g, c);                    // F' = G' + 2Z^2, lazy
-  ge r;
+// The formulas of the variable-base chain (ge_double_fast, ge_double_neg, ge_to_cached, ge_add_cached,
+// ge_scalar_mul_w4) are templates on the field type F: fe (fq29.hpp) everywhere, fes (fqs29.hpp, signed limbs)
+// in the per-lane window loop of k_scalar_mul_var / k_scalar_mul_var_el.  The statements are the same; what
+// "carried" and "lazy" mean below is fe's (fes never needs the carry a comment asks for, but runs it where written).
+template <class F>
+D377_HD ge_of<F> ge_double_fast(const ge_of<F>& p, bool with_t) {
+  F a = fe_sqr(p.x), b = fe_sqr(p.y);
+  F c = fe_sqr2x(p.z);                    // 2 Z^2 for the price of Z^2
+  F s_ = fe_sqr(fe_add(p.x, p.y));
+  F h = fe_add(a, b);                     // H' lazy
+  F e = fe_sub(h, s_);                    // E' = A + B - (X+Y)^2, carried
+  F g = fe_sub(a, b);                     // G' carried
+  F f = fe_add(g, c);                     // F' = G' + 2Z^2, lazy
+  ge_of<F> r;
   r.x = fe_mul(e, f); r.y = fe_mul(g, h); r.z = fe_mul(f, g);
   r.t = p.t;
   if (with_t) r.t = fe_mul(e, h);
@@ -911,14 +931,15 @@ D377_HD ge ge_double_fast(const ge& p, bool with_t) {
 // result is (-X3, Y3, Z3, -T3) = -[2]P -- and the (X+Y)^2 squaring with its offset subtraction
 // and carry pass (222 instructions) becomes one addition and one product (205).  An even number
 // of these in a row (the 4 per window) restores the sign.
-D377_HD ge ge_double_neg(const ge& p, bool with_t) {
-  fe a = fe_sqr(p.x), b = fe_sqr(p.y);
-  fe c = fe_sqr2x(p.z);
-  fe e = fe_mul(p.x, fe_dbl(p.y));        // 2XY
-  fe h = fe_add(a, b);                    // lazy
-  fe g = fe_sub(a, b);                    // carried
-  fe f = fe_add(g, c);                    // lazy
-  ge r;
+template <class F>
+D377_HD ge_of<F> ge_double_neg(const ge_of<F>& p, bool with_t) {
+  F a = fe_sqr(p.x), b = fe_sqr(p.y);
+  F c = fe_sqr2x(p.z);
+  F e = fe_mul(p.x, fe_dbl(p.y));         // 2XY
+  F h = fe_add(a, b);                     // lazy
+  F g = fe_sub(a, b);                     // carried
+  F f = fe_add(g, c);                     // lazy
+  ge_of<F> r;
   r.x = fe_mul(e, f); r.y = fe_mul(g, h); r.z = fe_mul(f, g);
   r.t = p.t;
   if (with_t) r.t = fe_mul(e, h);
@@ -929,27 +950,29 @@ D377_HD ge ge_double_neg(const ge& p, bool with_t) {
 // pad instructions, so a lone wave issues it as fast as it can issue anything (~4.6 cycles each)
 D377_HD ge ge_double_latency(const ge& p) { return ge_double_fast(p, true); }
 
-D377_HD gec ge_to_cached(const ge& p) {
-  gec c;
+template <class F>
+D377_HD gec_of<F> ge_to_cached(const ge_of<F>& p) {
+  gec_of<F> c;
   c.ypx = fe_carry(fe_add(p.y, p.x));     // carried, like ymx: a negative digit swaps the two
   c.ymx = fe_sub(p.y, p.x);               // carried
   c.z2 = fe_dbl(p.z);                     // lazy
-  c.kt = fe_mul(fe_const(FE_K), p.t);
+  c.kt = fe_mul(fe_as<F>(fe_const(FE_K)), p.t);
   return c;
 }
 
 // p + (neg ? -q : q).  The caller has already swapped q.ypx / q.ymx for a negative digit (the
 // table loader does it by address); the sign of 2dT is applied here by swapping F and G.
 // p's coordinates are products; q.ymx is carried, so Y - X needs no carry pass before it.
-D377_HD ge ge_add_cached(const ge& p, const gec& q, bool neg, bool with_t) {
-  fe a = fe_mul(fe_sub_nc(p.y, p.x), q.ymx);
-  fe b = fe_mul(fe_add(p.y, p.x), q.ypx);
-  fe c = fe_mul(p.t, q.kt);
-  fe d = fe_mul(p.z, q.z2);
-  fe e = fe_sub(b, a), h = fe_add(b, a);
-  fe dmc = fe_sub(d, c), dpc = fe_add(d, c);
-  fe f = fe_select(neg, dpc, dmc), g = fe_select(neg, dmc, dpc);
-  ge r;
+template <class F>
+D377_HD ge_of<F> ge_add_cached(const ge_of<F>& p, const gec_of<F>& q, bool neg, bool with_t) {
+  F a = fe_mul(fe_sub_nc(p.y, p.x), q.ymx);
+  F b = fe_mul(fe_add(p.y, p.x), q.ypx);
+  F c = fe_mul(p.t, q.kt);
+  F d = fe_mul(p.z, q.z2);
+  F e = fe_sub(b, a), h = fe_add(b, a);
+  F dmc = fe_sub(d, c), dpc = fe_add(d, c);
+  F f = fe_select(neg, dpc, dmc), g = fe_select(neg, dmc, dpc);
+  ge_of<F> r;
   r.x = fe_mul(e, f); r.y = fe_mul(g, h); r.z = fe_mul(f, g);
   r.t = p.t;
   if (with_t) r.t = fe_mul(e, h);
@@ -1003,16 +1026,20 @@ D377_HD ge ge_from_cached_affine(const gea& q, bool neg) {
 // `Tab` holds the per-lane table of cached 0..8 * P (global scratch on the GPU): it provides
 // store(j, gec) and load(j, swap) -> gec, where swap exchanges ypx / ymx (negative digit).
 // want_t: whether the caller uses T of the result (the square-root-free compressor does not).
-template <class Tab>
-D377_HD ge ge_scalar_mul_w4(const ge& p, const uint32_t digits[8], Tab& tab, bool want_t = true) {
+// F: the field type of the table and the loop (fes: Tab stores and loads gec_of<fes>); p and the result are fe points
+// (fe -> fes is free; at the end each coordinate goes back to a carried fe, fe_unsigned: no product).
+template <class F = fe, class Tab>
+D377_HD ge ge_scalar_mul_w4(const ge& p0, const uint32_t digits[8], Tab& tab, bool want_t = true) {
+  const ge_of<F> p = ge_as<F>(p0);
   {
-    gec id;
-    id.ypx = fe_const(FE_ONE); id.ymx = fe_const(FE_ONE); id.z2 = fe_dbl(fe_const(FE_ONE)); id.kt = fe_zero();
+    gec_of<F> id;
+    id.ypx = fe_as<F>(fe_const(FE_ONE)); id.ymx = fe_as<F>(fe_const(FE_ONE)); id.z2 = fe_dbl(fe_as<F>(fe_const(FE_ONE)));
+    id.kt = fe_as<F>(fe_zero());
     tab.store(0, id);
   }
-  const gec pc = ge_to_cached(p);
+  const gec_of<F> pc = ge_to_cached(p);
   tab.store(1, pc);
-  ge acc = ge_double_fast(p, true);
+  ge_of<F> acc = ge_double_fast(p, true);
   tab.store(2, ge_to_cached(acc));
 #pragma unroll 1
   for (int j = 3; j <= 8; ++j) {
@@ -1020,19 +1047,19 @@ D377_HD ge ge_scalar_mul_w4(const ge& p, const uint32_t digits[8], Tab& tab, boo
     tab.store(j, ge_to_cached(acc));
   }
   int d = fr_digit(digits, 63);                 // 0 or 1
-  ge r = ge_select(d != 0, p, ge_identity());
+  ge_of<F> r = ge_as<F>(ge_select(d != 0, p0, ge_identity()));
 #pragma unroll 1
   for (int i = 62; i >= 0; --i) {
     // fetch this window's table entry first: its ~1-2 us of memory latency hides under the
     // four doublings instead of stalling the addition
     d = fr_digit(digits, i);
     const bool neg = d < 0;
-    const gec e = tab.load(neg ? -d : d, neg);
+    const gec_of<F> e = tab.load(neg ? -d : d, neg);
 #pragma unroll 1
     for (int j = 0; j < 4; ++j) r = ge_double_neg(r, j == 3);   // (-2)^4 = 16
     r = ge_add_cached(r, e, neg, want_t && i == 0);   // only the last T can have a reader
   }
-  return r;
+  return ge_unsigned(r);
 }
 
 // signed radix-256 recoding of k < 2^251: k = sum d_i 256^i, d_i in [-128, 128), i = 0..31

@@ -36,21 +36,23 @@ namespace {
 // per-lane window table of the variable-base kernel in global scratch, laid out
 // [entry][thread][4 slots x 12 words]: a wave stores one entry as 12 KiB contiguous, and a lane
 // fetches its 192-byte (three 64-B sectors) record with 16-byte loads.  A negative digit
-// swaps the ypx / ymx slots by address.
+// swaps the ypx / ymx slots by address.  F: the field type of the chain that uses it (fes: the signed window loop,
+// same records bit for bit).
+template <class F>
 struct GlobalTab {
   uint32_t* base;
   size_t nthreads, tid;
-  __device__ __forceinline__ void store(int j, const gec& c) {
+  __device__ __forceinline__ void store(int j, const gec_of<F>& c) {
     uint32_t* p = base + ((size_t)j * nthreads + tid) * VB_ENTRY_WORDS;
     slot_store(p, c.ypx); slot_store(p + SLOT, c.ymx); slot_store(p + 2 * SLOT, c.z2); slot_store(p + 3 * SLOT, c.kt);
   }
-  __device__ __forceinline__ gec load(int j, bool swap) const {
+  __device__ __forceinline__ gec_of<F> load(int j, bool swap) const {
     const uint32_t* p = base + ((size_t)j * nthreads + tid) * VB_ENTRY_WORDS;
-    gec c;
-    c.ypx = slot_load(p + (swap ? SLOT : 0));
-    c.ymx = slot_load(p + (swap ? 0 : SLOT));
-    c.z2 = slot_load(p + 2 * SLOT);
-    c.kt = slot_load(p + 3 * SLOT);
+    gec_of<F> c;
+    c.ypx = slot_load_as<F>(p + (swap ? SLOT : 0));
+    c.ymx = slot_load_as<F>(p + (swap ? 0 : SLOT));
+    c.z2 = slot_load_as<F>(p + 2 * SLOT);
+    c.kt = slot_load_as<F>(p + 3 * SLOT);
     return c;
   }
 };
@@ -433,7 +435,7 @@ __global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD) k_scalar_mul_var(SqrtTa
                                                           uint8_t* status, uint32_t* scratch, DcbScratch dcb) {
   D377_POW_LDS();
   D377_DCB_BEGIN(out32);
-  GlobalTab tab;
+  GlobalTab<fes> tab;                                   // the window loop in signed limbs (fqs29.hpp)
   tab.base = scratch;
   tab.nthreads = (size_t)dcb.nslots * BLOCK;            // the window tables exist for this kernel's sets only (vb_scratch)
   tab.tid = io.lane;
@@ -454,7 +456,7 @@ __global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD) k_scalar_mul_var(SqrtTa
       fr_reduce_words(k);
       fr_half_words(k);
       fr_recode_signed16(k, dg);
-      const ge r = ge_scalar_mul_w4(g, dg, tab, DCB_WANT_T);
+      const ge r = ge_scalar_mul_w4<fes>(g, dg, tab, DCB_WANT_T);     // (r: back in fe, carried)
       D377_INVARIANT(T, r, bad == 0);
       dcb_put(io, j, ge_dcb_from_half(r, bad != 0));      // failed lanes: neutral state, all-zero output
     });
@@ -943,7 +945,7 @@ __global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD) k_scalar_mul_var_el(con
   // chunked like the kernels above (one workgroup per per_lane x 256 elements, a claimed set of window tables)
   const int slot = dcb_claim(dcb);
   if (slot < 0) return;
-  GlobalTab tab;
+  GlobalTab<fes> tab;                                   // the window loop in signed limbs (fqs29.hpp)
   tab.base = scratch;
   tab.nthreads = (size_t)dcb.nslots * BLOCK;
   tab.tid = (size_t)slot * BLOCK + threadIdx.x;
@@ -963,7 +965,7 @@ __global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD) k_scalar_mul_var_el(con
       const ge g = load_ge_mont256(xyzt, i);
       fr_reduce_words(k);
       fr_recode_signed16(k, dg);
-      store_ge_mont256(out, i, ge_scalar_mul_w4(g, dg, tab));
+      store_ge_mont256(out, i, ge_scalar_mul_w4<fes>(g, dg, tab));
     }
   }
   dcb_release(dcb, slot);

@@ -77,6 +77,22 @@ __device__ __forceinline__ fe slot_load(const uint32_t* p) {
   r.l[8] = c.x;
   return r;
 }
+// the same 48-byte slot holding a signed-limb element (fqs29.hpp): the limbs' bit patterns
+__device__ __forceinline__ void slot_store(uint32_t* p, const fes& v) {
+  uint4* q = reinterpret_cast<uint4*>(p);
+  q[0] = make_uint4((uint32_t)v.l[0], (uint32_t)v.l[1], (uint32_t)v.l[2], (uint32_t)v.l[3]);
+  q[1] = make_uint4((uint32_t)v.l[4], (uint32_t)v.l[5], (uint32_t)v.l[6], (uint32_t)v.l[7]);
+  q[2] = make_uint4((uint32_t)v.l[8], 0, 0, 0);
+}
+template <class F> __device__ __forceinline__ F slot_load_as(const uint32_t* p);
+template <> __device__ __forceinline__ fe slot_load_as<fe>(const uint32_t* p) { return slot_load(p); }
+template <> __device__ __forceinline__ fes slot_load_as<fes>(const uint32_t* p) {
+  const fe u = slot_load(p);
+  fes r;
+#pragma unroll
+  for (int i = 0; i < NL; ++i) r.l[i] = (int32_t)u.l[i];
+  return r;
+}
 
 // Cached AFFINE point record: Y+X, Y-X (both carried: a negative digit swaps them), 2dXY -- 27 limbs packed into a
 // 128-byte, 128-byte-aligned slot, fetched as seven 16-byte loads = exactly two 64-byte sectors per gather.  (Three
