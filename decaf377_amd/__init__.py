@@ -10,10 +10,11 @@ from .engine import (  # noqa: F401
     Element,
     Encoding,
     EncodingError,
+    FixedBases,
     Fq,
     Fr,
     default_context,
 )
 
-__all__ = ["Context", "Element", "Encoding", "EncodingError", "Fq", "Fr", "default_context",
+__all__ = ["Context", "Element", "Encoding", "EncodingError", "FixedBases", "Fq", "Fr", "default_context",
            "NativeError", "StarvedError", "load", "LIB_PATH"]

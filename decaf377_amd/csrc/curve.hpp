@@ -1150,6 +1150,50 @@ D377_HD ge ge_scalar_mul_base_w8(const uint32_t k[8], const FTab& ftab, bool wan
   }
   return r;
 }
+// The same walk over the combs of m bases (d377_batch_fixed_msm): sum_j k_j * B_j, m x W mixed additions into ONE
+// accumulator.  `kload(j, k)` leaves base j's scalar in k as the caller wants it walked (reduced, and halved for the
+// encoding); `ftab.load(j, i, d, swap)` is entry d of window i of base j's comb.  One entry is in flight across the
+// whole sequence, the boundary between two bases included, and only the very first record is lifted
+// (ge_from_cached_affine); every later one, the first window of each further base among them, is an addition.
+template <int BITS, class FTab, class KLoad>
+D377_HD ge ge_fixed_msm_w8(int m, KLoad&& kload, const FTab& ftab, bool want_t = true) {
+  constexpr int W = FbShape<BITS>::windows;
+  uint32_t k[8];
+  kload(0, k);
+  uint32_t carry = 0;
+  int d = fb_digit<BITS>(k, 0, carry);
+  bool neg = d < 0;
+  gea e = ftab.load(0, 0, neg ? -d : d, neg);
+  ge r;
+  {
+    const gea cur = e;
+    const bool neg_cur = neg;
+    d = fb_digit<BITS>(k, 1, carry);
+    neg = d < 0;
+    e = ftab.load(0, 1, neg ? -d : d, neg);
+    r = ge_from_cached_affine(cur, neg_cur);
+  }
+  const int total = m * W;
+  int j = 0, i = 1;                                    // base and window of the entry in flight
+#pragma unroll 1
+  for (int s = 1; s < total; ++s) {
+    const gea cur = e;
+    const bool neg_cur = neg;
+    if (s + 1 < total) {
+      if (++i == W) {                                  // every digit of base j is out: its scalar words are free
+        i = 0;
+        ++j;
+        kload(j, k);
+        carry = 0;
+      }
+      d = fb_digit<BITS>(k, i, carry);
+      neg = d < 0;
+      e = ftab.load(j, i, neg ? -d : d, neg);
+    }
+    r = ge_add_affine(r, cur, neg_cur, want_t || s + 1 < total);
+  }
+  return r;
+}
 
 // generic x^e for a 256-bit exponent given as 8 words (init kernels only: inversion by q - 2)
 D377_HD fe fe_pow_words(const fe& x, const uint32_t (&e)[8]) {

@@ -26,6 +26,7 @@
 #include "row_ops.hpp"
 #include "host_state.hpp"
 #include "codec_chunked.hpp"
+#include "fixed_comb.hpp"
 
 using namespace d377;
 
@@ -132,12 +133,7 @@ __global__ void __launch_bounds__(BLOCK) k_init_slookup(uint8_t* s_lookup, uint3
   }
 }
 
-// FB[i][j] = j * 2^(FB_BITS i) * B in affine cached form, i < FB_WINDOWS, j < FB_ENTRIES.  A thread builds a RUN of
-// FB_RUN consecutive multiples of one window: j0 * base by double-and-add, then one addition of the base per entry; the
-// projective coordinates are parked in the entries' own records (27 limbs = a record's 27 words) and the run's Z's are
-// inverted together (Montgomery's trick: one divsteps inversion per FB_RUN entries).  ~9 000 instructions per entry;
-// one thread per entry with its own ladder from B and its own inversion was ~420 000 at 21-bit windows (12.6 M entries).
-constexpr int FB_RUN = 16;
+// the generator comb's window bases; the comb itself is built by k_init_fbase (fixed_comb.hpp)
 template <int FB_BITS>
 __global__ void k_init_fbase_bases(uint32_t* bases) {          // bases[i] = 2^(FB_BITS i) * B as X, Y, Z, T: one thread
   constexpr int FB_WINDOWS = FbShape<FB_BITS>::windows;
@@ -151,51 +147,6 @@ __global__ void k_init_fbase_bases(uint32_t* bases) {          // bases[i] = 2^(
     for (int k = 0; k < FB_BITS; ++k) p = ge_double(p);
   }
 }
-template <int FB_BITS>
-__global__ void __launch_bounds__(BLOCK) k_init_fbase(const uint32_t* bases, uint32_t* fb) {
-  constexpr int FB_WINDOWS = FbShape<FB_BITS>::windows, FB_ENTRIES = FbShape<FB_BITS>::entries;
-  constexpr int RUNS = (FB_ENTRIES + FB_RUN - 1) / FB_RUN;
-  const size_t idx = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (idx >= (size_t)FB_WINDOWS * RUNS) return;
-  const int i = (int)(idx / RUNS), j0 = (int)(idx % RUNS) * FB_RUN;
-  ge base;
-  base.x = slot_load(bases + (size_t)i * 4 * SLOT); base.y = slot_load(bases + (size_t)i * 4 * SLOT + SLOT);
-  base.z = slot_load(bases + (size_t)i * 4 * SLOT + 2 * SLOT); base.t = slot_load(bases + (size_t)i * 4 * SLOT + 3 * SLOT);
-  ge acc = ge_identity();
-#pragma unroll 1
-  for (int b = FB_BITS - 1; b >= 0; --b) {                     // acc = j0 * base
-    acc = ge_double(acc);
-    if ((j0 >> b) & 1) acc = ge_add(acc, base);
-  }
-  uint32_t* rec0 = fb + ((size_t)i * FB_ENTRIES + j0) * FBW_ENTRY_WORDS;
-  fe prefix[FB_RUN];
-  fe c = fe_const(FE_ONE);
-#pragma unroll
-  for (int r = 0; r < FB_RUN; ++r) {
-    if (j0 + r < FB_ENTRIES) {
-      uint32_t* q = rec0 + (size_t)r * FBW_ENTRY_WORDS;
-#pragma unroll
-      for (int k = 0; k < NL; ++k) { q[k] = acc.x.l[k]; q[NL + k] = acc.y.l[k]; q[2 * NL + k] = acc.z.l[k]; }
-      prefix[r] = c;
-      c = fe_mul(c, acc.z);
-      acc = ge_add(acc, base);
-    }
-  }
-  fe inv = fe_invert(c);
-#pragma unroll
-  for (int r = FB_RUN - 1; r >= 0; --r) {
-    if (j0 + r < FB_ENTRIES) {
-      uint32_t* q = rec0 + (size_t)r * FBW_ENTRY_WORDS;
-      fe X, Y, Z;
-#pragma unroll
-      for (int k = 0; k < NL; ++k) { X.l[k] = q[k]; Y.l[k] = q[NL + k]; Z.l[k] = q[2 * NL + k]; }
-      const fe zi = fe_mul(inv, prefix[r]);
-      inv = fe_mul(inv, Z);
-      pt_store_affine(q, gea_from_affine(fe_mul(X, zi), fe_mul(Y, zi)));
-    }
-  }
-}
-
 // --------------------------------------------------------------------------- batch kernels ---
 // The kernels that work in chunks (dcb_rounds above) hand their square roots the inverses of their denominators.
 __global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD) k_sqrt_ratio_zeta(SqrtTables T, const uint8_t* num32,
@@ -1443,7 +1394,7 @@ int ensure_comb(DeviceState& d, hipStream_t s) {
     }
     hipLaunchKernelGGL(k_init_fbase_bases<BITS>, dim3(1), dim3(64), 0, d.stream, d.fb_bases);
     const size_t runs = (size_t)Sh::windows * ((Sh::entries + FB_RUN - 1) / FB_RUN);
-    hipLaunchKernelGGL(k_init_fbase<BITS>, dim3((unsigned)((runs + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, d.stream, d.fb_bases, fb);
+    hipLaunchKernelGGL(k_init_fbase<BITS>, dim3((unsigned)((runs + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, d.stream, d.fb_bases, fb, (size_t)Sh::windows);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
     if (e != hipSuccess) { (void)hipFree(fb); return fail(D377_ERR_HIP, "building the fixed-base comb: %s", hipGetErrorString(e)); }
@@ -2210,6 +2161,7 @@ int d377_ctx_create_ex(const int* device_ids, int n_dev, const d377_ctx_opts* op
 
 void d377_ctx_destroy(d377_ctx* ctx) {
   if (!ctx) return;
+  fixed_bases_release_all(ctx);                                 // handles still alive: their tables go first, then the devices
   for (auto& d : ctx->devs) free_device(d);
   delete ctx;
 }

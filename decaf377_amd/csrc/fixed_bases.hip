@@ -1,0 +1,336 @@
+// fixed_bases.hip -- fixed-base combs for caller-chosen points and many sums over them (gfx950):
+//   d377_fixed_bases_create   one comb per base on every device (fixed_comb.hpp: k_fb_window_bases, then ONE k_init_fbase
+//                             launch over the m x W windows of all bases)
+//   d377_batch_fixed_msm      out[i] = sum_j scalar[i m + j] * B_j, one lane per sum
+//
+// The sum is k_scalar_mul_base's walk widened to m combs (curve.hpp: ge_fixed_msm_w8): each base's scalar is reduced and
+// halved, its W signed digits pick one entry per window, and all m x W mixed additions go into ONE accumulator -- no
+// doubling anywhere.  The walk yields H = sum_j (k_j / 2 mod r) B_j, and the encoding of 2 H comes out of the square-root-free
+// compressor (ge_dcb_from_half), its inversion shared with the chunk's other sums (dcb.hpp), as for the generator comb.
+// Against d377_batch_msm_small's Straus chain (252 doublings + 64 m additions + m window tables per sum) this is 14-32 mixed
+// additions per base and nothing else.
+//
+// A translation unit of its own, like batch_msm.hip: the register tables of d377.hip's kernels are measured artefacts.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+#include <algorithm>
+#include <chrono>
+#include <mutex>
+#include <new>
+#include <string>
+#include <thread>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/decaf377_amd.h"
+#include "curve.hpp"
+#include "device_util.hpp"
+#include "dcb.hpp"
+#include "host_state.hpp"
+#include "fixed_comb.hpp"
+
+using namespace d377;
+
+namespace {
+
+constexpr int FX_MAX = D377_FIXED_BASES_MAX;
+
+// the m combs of a handle, back to back: entry c of window i of base j
+template <int BITS>
+struct CombTabs {
+  const uint32_t* base;
+  __device__ __forceinline__ gea load(int j, int i, int c, bool swap) const {
+    return pt_load_affine(base + (((size_t)j * FbShape<BITS>::windows + i) * FbShape<BITS>::entries + c) * FBW_ENTRY_WORDS, swap);
+  }
+};
+
+// One lane per sum, in chunks like k_scalar_mul_base (dcb.hpp): the sums of a chunk share one inversion per wave.  No table
+// scratch -- the combs are the handle's -- so the lane sets are only the round records.
+template <int BITS>
+__global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD)
+k_fixed_msm_lane(SqrtTables T, const uint32_t* tabs, const uint8_t* scalar32, int m, size_t n, uint8_t* out32, uint64_t* xyzt_out,
+                 DcbScratch dcb) {
+  __shared__ uint32_t lds_pow_[1];                                 // (no square root here: residency is set by the launch's padding)
+  LdsPowTab pt;
+  pt.col = lds_pow_;
+  D377_DCB_BEGIN(out32);
+  const CombTabs<BITS> ft{tabs};
+  dcb_rounds<0, true>(n, io, pt,
+    [&](size_t, int) {},
+    [&](size_t i, int j, const uint32_t (*)[8], bool) {
+      const size_t first = i * (size_t)m;
+      const ge r = ge_fixed_msm_w8<BITS>(m, [&](int p, uint32_t k[8]) {
+        load32(scalar32, first + (size_t)p, k);
+        fr_reduce_words(k);
+        fr_half_words(k);                                          // the walk yields H = sum (k / 2) B: the encoding of 2 H needs no root
+      }, ft, DCB_WANT_T);
+      D377_INVARIANT(T, r, true);
+      if (xyzt_out) store_ge_mont256(xyzt_out, i, ge_double_fast(r, true));   // the sum itself is the double
+      dcb_put(io, j, ge_dcb_from_half(r, false));
+    });
+  D377_DCB_END();
+}
+
+// ------------------------------------------------------------------------------ host side ---
+// The comb widths a handle may ask for; f(std::integral_constant<int, BITS>) runs with the kernels of that width.
+int width_slot(int bits) { return bits == 8 ? 0 : bits == 12 ? 1 : bits == 16 ? 2 : bits == 18 ? 3 : -1; }
+template <class F>
+int with_width(int bits, F&& f) {
+  switch (bits) {
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 18: return f(std::integral_constant<int, 18>{});
+  }
+  return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create: comb_bits must be 8, 12, 16 or 18 (0 = 16)");
+}
+template <int BITS>
+size_t comb_bytes() { return (size_t)FbShape<BITS>::windows * FbShape<BITS>::entries * FBW_ENTRY_WORDS * sizeof(uint32_t); }
+
+// Residency of the lane kernel against the lane sets (as d377_ctx_create checks the kernels of d377.hip): at most
+// WAVES_PER_SIMD workgroups per CU, padded with dynamic LDS where registers alone would let more in.  Once per device and
+// width, by d377_fixed_bases_create; the caller holds ctx->mu.
+template <int BITS>
+int check_residency_fx(DeviceState& d) {
+  int& lds = d.fx_lds[width_slot(BITS)];
+  if (lds >= 0) return D377_OK;
+  const void* fn = reinterpret_cast<const void*>(k_fixed_msm_lane<BITS>);
+  int nb = 0;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, 0));
+  int pad = 0;
+  if (nb > WAVES_PER_SIMD) {
+    pad = (160 * 1024) / (WAVES_PER_SIMD + 1) + 1024;
+    if (pad > 64 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, pad));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, (size_t)pad));
+  }
+  if (getenv("D377_DEBUG_RESIDENCY"))
+    fprintf(stderr, "d377: k_fixed_msm_lane<%d>: %d workgroups per CU with %d bytes of LDS padding\n", BITS, nb, pad);
+  if (nb < 1 || nb > WAVES_PER_SIMD)
+    return fail(D377_ERR_INIT, "residency of %s does not match the lane sets of the scratch areas", "k_fixed_msm_lane");
+  lds = pad;
+  return D377_OK;
+}
+
+// the combs of `m` bases on one device: residency check, allocation, window bases, one build launch, synchronised.
+// On failure nothing of this device is left allocated.  Caller holds ctx->mu.
+template <int BITS>
+int build_on(DeviceState& d, const uint64_t* xyzt, size_t m, uint32_t** out) {
+  using Sh = FbShape<BITS>;
+  *out = nullptr;
+  HIP_TRY(hipSetDevice(d.id));
+  int rc = check_residency_fx<BITS>(d);
+  if (rc) return rc;
+  const size_t bytes = m * comb_bytes<BITS>(), nwin = m * (size_t)Sh::windows;
+  uint32_t* tab = nullptr;
+  uint64_t* rec = nullptr;
+  uint32_t* wb = nullptr;
+  auto cleanup = [&]() { (void)hipFree(tab); (void)hipFree(rec); (void)hipFree(wb); };
+  if (hipMalloc(&tab, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    tab = nullptr;
+    snprintf(d377_g_err, sizeof d377_g_err,
+             "d377_fixed_bases_create: the combs need %.3f GB of device memory and the allocation failed (device %d): fewer bases or a "
+             "narrower comb_bits", (double)bytes / 1e9, d.id);
+    return D377_ERR_HIP;
+  }
+  if (hipMalloc(&rec, m * 16 * sizeof(uint64_t)) != hipSuccess || hipMalloc(&wb, nwin * 4 * SLOT * sizeof(uint32_t)) != hipSuccess) {
+    (void)hipGetLastError();
+    cleanup();
+    return fail(D377_ERR_HIP, "%s", "d377_fixed_bases_create: hipMalloc failed (window bases)");
+  }
+  hipError_t e = hipMemcpyAsync(rec, xyzt, m * 16 * sizeof(uint64_t), hipMemcpyHostToDevice, d.stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_fb_window_bases<BITS>, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, d.stream, rec, (int)m, wb);
+    const size_t runs = nwin * ((Sh::entries + FB_RUN - 1) / FB_RUN);
+    hipLaunchKernelGGL(k_init_fbase<BITS>, dim3((unsigned)((runs + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, d.stream, wb, tab, nwin);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+  (void)hipFree(rec); rec = nullptr;
+  (void)hipFree(wb); wb = nullptr;
+  if (e != hipSuccess) {
+    cleanup();
+    return fail(D377_ERR_HIP, "d377_fixed_bases_create: building the combs: %s", hipGetErrorString(e));
+  }
+  *out = tab;
+  return D377_OK;
+}
+
+// everything on device pointers, enqueued on `s`; the caller holds ctx->mu
+int fixed_msm_launch(DeviceState& d, hipStream_t s, const FixedBases& fb, const uint32_t* tab, const uint8_t* scalars, size_t n,
+                     uint8_t* out32, uint64_t* xyzt_out) {
+  if (n == 0) return D377_OK;
+  const int lds = d.fx_lds[width_slot(fb.bits)];
+  if (lds < 0) return fail(D377_ERR_INIT, "%s", "k_fixed_msm_lane: residency not checked on this device");
+  GuardScope vb{d.vb_guard, s};                              // the lane-set areas: queue behind their last user
+  int rc;
+  if ((rc = vb.acquire())) return rc;
+  const size_t places = (size_t)d.cus * WAVES_PER_SIMD, rounds = (n + BLOCK - 1) / BLOCK;
+  const ChunkDeal c = deal_chunks(rounds, places, (size_t)DCB_K, (size_t)d.cus * 64);
+  DcbScratch dcb{d.dcb_scratch, d.slot_pool, d.cus * WAVES_PER_SIMD, (int)c.per_lane, d.dcb_sets * BLOCK, (int)c.extra, d.pool_health};
+  dcb.prio = c.nchunks <= 2 * places ? 1 : 0;               // as d377.hip's chunks_of
+  const SqrtTables T = d.tables();
+  if ((rc = with_width(fb.bits, [&](auto b) -> int {
+         hipLaunchKernelGGL(k_fixed_msm_lane<decltype(b)::value>, dim3((unsigned)c.nchunks), dim3(BLOCK), lds, s, T, tab, scalars,
+                            (int)fb.m, n, out32, xyzt_out, dcb);
+         return D377_OK; }))) return rc;
+  HIP_TRY(hipGetLastError());
+  return vb.finish();
+}
+
+// one device's slice of a host batch: copies in, kernel, copies out, synchronised
+int fixed_msm_one(DeviceState& d, const FixedBases& fb, const uint32_t* tab, const uint8_t* scalars, size_t n, uint8_t* out32,
+                  uint64_t* xyzt_out) {
+  if (n == 0) return D377_OK;
+  HIP_TRY(hipSetDevice(d.id));
+  int rc = D377_OK;
+  SyncOnError guard{&rc, d.id, d.stream, nullptr};
+  auto body = [&]() -> int {
+    const size_t terms = n * fb.m;
+    int r;
+    if ((r = ensure(d, 1, terms * 32))) return r;
+    if ((r = ensure(d, 2, n * (xyzt_out ? 32 + 128 : 32)))) return r;      // the Encodings, then the Element records
+    StarveCheck starve{d, d.stream};
+    if ((r = starve.before())) return r;
+    HIP_TRY(hipMemcpyAsync(d.buf[1], scalars, terms * 32, hipMemcpyHostToDevice, d.stream));
+    uint64_t* xyzt_dev = xyzt_out ? reinterpret_cast<uint64_t*>(d.buf[2] + n * 32) : nullptr;
+    if ((r = fixed_msm_launch(d, d.stream, fb, tab, d.buf[1], n, d.buf[2], xyzt_dev))) return r;
+    HIP_TRY(hipMemcpyAsync(out32, d.buf[2], n * 32, hipMemcpyDeviceToHost, d.stream));
+    if (xyzt_out) HIP_TRY(hipMemcpyAsync(xyzt_out, xyzt_dev, n * 128, hipMemcpyDeviceToHost, d.stream));
+    if ((r = starve.after())) return r;
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    return starve.verdict();
+  };
+  rc = body();
+  return rc;
+}
+
+// frees a registration's tables (every device); caller holds ctx->mu or is destroying the context
+void free_tables(d377_ctx* ctx, FixedBases* fb) {
+  for (size_t k = 0; k < fb->tab.size(); ++k) {
+    if (!fb->tab[k]) continue;
+    DeviceState& d = ctx->devs[k];
+    (void)hipSetDevice(d.id);
+    if (d.stream) (void)hipStreamSynchronize(d.stream);
+    (void)d.vb_guard.drain();                                // a launch on the table may be in flight on another stream
+    (void)hipFree(fb->tab[k]);
+    fb->tab[k] = nullptr;
+  }
+}
+
+// the live registration `handle` of the context, or null; caller holds ctx->mu
+FixedBases* find(d377_ctx* ctx, int64_t handle) {
+  for (FixedBases* fb : ctx->fixed)
+    if (fb->handle == handle) return fb;
+  return nullptr;
+}
+
+}  // namespace
+
+namespace d377 {
+void fixed_bases_release_all(d377_ctx* ctx) {
+  for (FixedBases* fb : ctx->fixed) {
+    free_tables(ctx, fb);
+    delete fb;
+  }
+  ctx->fixed.clear();
+}
+}  // namespace d377
+
+extern "C" {
+
+int d377_fixed_bases_create(d377_ctx* ctx, const uint64_t* xyzt, size_t m, int comb_bits, int64_t* handle_out) {
+  if (handle_out) *handle_out = 0;
+  if (m < 1 || m > (size_t)FX_MAX)
+    return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create: m must be 1 .. 64 bases (D377_FIXED_BASES_MAX)");
+  const int bits = comb_bits == 0 ? 16 : comb_bits;
+  if (width_slot(bits) < 0) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create: comb_bits must be 8, 12, 16 or 18 (0 = 16)");
+  if (!xyzt) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create: xyzt is null");
+  if (!handle_out) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create: handle_out is null");
+  if (!ctx) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create: ctx is null");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  FixedBases* fb = new (std::nothrow) FixedBases;
+  if (!fb) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create: out of host memory");
+  fb->m = m;
+  fb->bits = bits;
+  fb->tab.assign(ctx->devs.size(), nullptr);
+  int rc = with_width(bits, [&](auto b) -> int {
+    constexpr int BITS = decltype(b)::value;
+    fb->bytes = (uint64_t)(m * comb_bytes<BITS>());
+    for (size_t k = 0; k < ctx->devs.size(); ++k) {
+      const int r = build_on<BITS>(ctx->devs[k], xyzt, m, &fb->tab[k]);
+      if (r) return r;
+    }
+    return D377_OK;
+  });
+  if (rc) {
+    char saved[sizeof d377_g_err];
+    memcpy(saved, d377_g_err, sizeof saved);
+    free_tables(ctx, fb);
+    delete fb;
+    memcpy(d377_g_err, saved, sizeof saved);
+    return rc;
+  }
+  fb->handle = ctx->next_fixed++;
+  ctx->fixed.push_back(fb);
+  *handle_out = fb->handle;
+  return D377_OK;
+}
+
+int d377_fixed_bases_info(d377_ctx* ctx, int64_t handle, uint64_t* m, int* comb_bits, uint64_t* table_bytes_per_device) {
+  if (!ctx) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_info: ctx is null");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  const FixedBases* fb = find(ctx, handle);
+  if (!fb) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_info: handle is not a live registration of this context");
+  if (m) *m = fb->m;
+  if (comb_bits) *comb_bits = fb->bits;
+  if (table_bytes_per_device) *table_bytes_per_device = fb->bytes;
+  return D377_OK;
+}
+
+int d377_fixed_bases_destroy(d377_ctx* ctx, int64_t handle) {
+  if (!ctx) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_destroy: ctx is null");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  FixedBases* fb = find(ctx, handle);
+  if (!fb) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_destroy: handle is not a live registration of this context");
+  ctx->fixed.erase(std::find(ctx->fixed.begin(), ctx->fixed.end(), fb));
+  free_tables(ctx, fb);
+  delete fb;
+  return D377_OK;
+}
+
+// host pointers: contiguous slices of the SUMS over the context's devices, one host thread per device (as batch_msm.hip)
+int d377_batch_fixed_msm(d377_ctx* ctx, int64_t handle, const uint8_t* scalar32, size_t n, uint8_t* enc32_out, uint64_t* xyzt_out) {
+  if (!ctx) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_msm: ctx is null");
+  if (n && (!scalar32 || !enc32_out)) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_msm: null buffer");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  const FixedBases* fb = find(ctx, handle);
+  if (!fb) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_msm: handle is not a live registration of this context");
+  if (n == 0) return D377_OK;
+  const size_t nd = ctx->devs.size(), m = fb->m;
+  if (nd == 1) return fixed_msm_one(ctx->devs[0], *fb, fb->tab[0], scalar32, n, enc32_out, xyzt_out);
+  const size_t per = (n + nd - 1) / nd;
+  std::vector<int> rcs(nd, D377_OK);
+  std::vector<std::string> errs(nd);
+  std::vector<std::thread> workers;
+  const int delay = debug_device_delay_ms();
+  for (size_t k = 0; k < nd; ++k) {
+    const size_t lo = per * k;
+    if (lo >= n) break;
+    const size_t cnt = (lo + per <= n) ? per : n - lo;
+    workers.emplace_back([&, k, lo, cnt]() {
+      if (delay > 0) std::this_thread::sleep_for(std::chrono::milliseconds(delay));
+      rcs[k] = fixed_msm_one(ctx->devs[k], *fb, fb->tab[k], scalar32 + lo * m * 32, cnt, enc32_out + lo * 32,
+                             xyzt_out ? xyzt_out + lo * 16 : nullptr);
+      if (rcs[k] != D377_OK) errs[k] = d377_g_err;
+    });
+  }
+  for (auto& w : workers) w.join();
+  for (size_t k = 0; k < nd; ++k)
+    if (rcs[k] != D377_OK) return fail(rcs[k], "%s", errs[k].c_str());
+  return D377_OK;
+}
+
+}  // extern "C"

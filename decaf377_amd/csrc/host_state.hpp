@@ -108,6 +108,7 @@ struct DeviceState {
   uint32_t* bm_scratch = nullptr;        // batch_msm.hip: tables and digit words of the batched small sums, per resident lane; grown on first use
   size_t bm_cap = 0;
   int bm_lds[2] = {-1, -1};              // batch_msm.hip: LDS padding of its lane kernel (Element / Encoding form), -1 = not asked yet
+  int fx_lds[4] = {-1, -1, -1, -1};      // fixed_bases.hip: LDS padding of its lane kernel per comb width (8 / 12 / 16 / 18), -1 = not asked yet
   uint32_t* gtab = nullptr;
   uint8_t* s_lookup = nullptr;
   uint32_t* fbase = nullptr;             // the fixed-base comb: null until built (d377.hip ensure_comb: at context creation, or by the first fixed-base call of a lazy context)
@@ -231,6 +232,11 @@ enum Op { OP_SQRT, OP_DECOMPRESS, OP_COMPRESS, OP_ROUNDTRIP, OP_MUL_BASE, OP_MUL
 // with a single GPU listed twice.
 int debug_device_delay_ms();
 
+// fixed_bases.hip: frees the tables of every registration of d377_fixed_bases_create still alive on the context (d377_ctx_destroy).
+// Caller holds no lock; the context is being destroyed, so no other call may be running on it.
+struct FixedBases;
+void fixed_bases_release_all(d377_ctx* ctx);
+
 }  // namespace d377
 
 struct d377_ctx {
@@ -238,4 +244,18 @@ struct d377_ctx {
   std::mutex mu;
   d377::Tuning tune;
   std::vector<int> peer;                  // [a][b]: 1 = the same physical device, 2 = peer access a -> b enabled by d377_ctx_create, 0 = none
+  std::vector<d377::FixedBases*> fixed;   // the live registrations of d377_fixed_bases_create (under mu): released with the context
+  int64_t next_fixed = 1;                 // the next handle d377_fixed_bases_create hands out
 };
+
+// One registration of d377_fixed_bases_create: one comb per base on every device of the context, the m combs of a device
+// in one allocation (fixed_comb.hpp).  Owned by the context's `fixed` list until d377_fixed_bases_destroy.
+namespace d377 {
+struct FixedBases {
+  int64_t handle = 0;
+  size_t m = 0;
+  int bits = 0;
+  uint64_t bytes = 0;                     // table bytes per device
+  std::vector<uint32_t*> tab;             // per device of the context, in its order
+};
+}  // namespace d377

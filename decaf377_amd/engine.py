@@ -7,6 +7,7 @@ Reference (crate decaf377 v0.10.1)              here (one call = one batch)
   Element::encode_to_curve(&Fq)                   Element.encode_to_curve(Fq) -> Encoding
   Element::hash_to_curve(&Fq, &Fq)                Element.hash_to_curve(Fq, Fq) -> Encoding
   Element::GENERATOR * Fr                         Element.generator_mul(Fr) -> Encoding
+  FixedBase tables over any Elements (ark-ec)     FixedBases(Element).vartime_multiscalar_mul(Fr) -> Encoding
   element * Fr  (Encoding in, Encoding out)       Encoding.scalar_mul(Fr) -> (Encoding, status)
   Fq::sqrt_ratio_zeta(&num, &den)                 Fq.sqrt_ratio_zeta(num, den) -> (was_square, Fq)
   EncodingError::InvalidEncoding                  status byte 1 (0 = Ok) / EncodingError when raised
@@ -171,8 +172,16 @@ class Context:
 
         return _Scope()
 
+    def fixed_bases(self, points, comb_bits=16):
+        """Registers 1 <= m <= 64 fixed bases ([m, 16] u64 Element records, numpy or torch) and builds one comb per base on
+        every device of the context (d377_fixed_bases_create): comb_bits 8 / 12 / 16 / 18 = 0.53 / 5.5 / 67 / 235 MB per base.
+        Returns a FixedBases; it keeps this context alive and is closed before it."""
+        return FixedBases(points, comb_bits=comb_bits, ctx=self)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
+            for fb in list(getattr(self, "_fixed", ())):          # handles first: d377_fixed_bases_destroy before d377_ctx_destroy
+                fb.close()
             self._lib.d377_ctx_destroy(self._h)
             self._h = ctypes.c_void_p()
 
@@ -561,6 +570,101 @@ class Context:
                                                       ctypes.c_void_p(xyzt.contiguous().data_ptr()), ctypes.c_size_t(m),
                                                       ctypes.c_void_p(enc.data_ptr()), ctypes.c_void_p(out.data_ptr())))
         return enc, out
+
+
+class FixedBases:
+    """Fixed-base combs for caller-chosen points (d377_fixed_bases_create / d377_batch_fixed_msm): the reference's
+    Element works with ark-ec's FixedBase window tables (src/ark_curve/element.rs:22-38); here one comb per base lives on
+    every device of the context and one call computes n sums
+
+        out[i] = scalars[i m] * B_0 + ... + scalars[i m + m - 1] * B_{m-1}
+
+    points: an Element batch or an [m, 16] u64 array of Element records (numpy or torch; read once, at creation).
+    comb_bits: 8, 12, 16 or 18.  ctx: the Context (default_context() if None); the FixedBases keeps it alive, and
+    Context.close() closes every FixedBases of the context first.  Usable as a context manager."""
+
+    def __init__(self, points, comb_bits=16, ctx=None):
+        if isinstance(points, Element):
+            ctx = ctx or points.ctx
+            points = points.data
+        self.ctx = ctx or default_context()
+        if _is_torch(points):
+            points = points.detach().cpu().numpy()
+        pts = np.ascontiguousarray(np.asarray(points).view(np.uint64) if np.asarray(points).dtype == np.int64 else points)
+        if pts.ndim != 2 or pts.shape[1] != 16 or pts.dtype != np.uint64:
+            raise ValueError("FixedBases: points must be [m, 16] u64 Element records")
+        self._lib = self.ctx._lib
+        self._h = 0
+        if not self.ctx._h:
+            raise _native.NativeError("FixedBases: the context is closed")
+        h = ctypes.c_int64(0)
+        _native.check(self._lib.d377_fixed_bases_create(self.ctx._h, pts.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(pts.shape[0]),
+                                                        int(comb_bits), ctypes.byref(h)))
+        self._h = int(h.value)
+        if not hasattr(self.ctx, "_fixed"):
+            import weakref
+            self.ctx._fixed = weakref.WeakSet()
+        self.ctx._fixed.add(self)
+        self.m, self.comb_bits, self.table_bytes = self.info()
+
+    def info(self):
+        """(m, comb width in bits, table bytes per device): d377_fixed_bases_info."""
+        m, b, t = ctypes.c_uint64(0), ctypes.c_int(0), ctypes.c_uint64(0)
+        _native.check(self._lib.d377_fixed_bases_info(self.ctx._h, self._live(), ctypes.byref(m), ctypes.byref(b), ctypes.byref(t)))
+        return int(m.value), int(b.value), int(t.value)
+
+    def _live(self):
+        if not self._h:
+            raise _native.NativeError("FixedBases: the handle is closed")
+        return self._h
+
+    def msm(self, scalar32, elements=False):
+        """n sums over the registered bases: scalar32 [n * m, 32] u8, term-major within a sum (any 32 bytes, reduced mod r)
+        -> enc [n, 32] u8, or (enc, xyzt [n, 16]) with elements=True.  A torch tensor is STAGED through host memory (the
+        library has no device-pointer form of this call) and the results come back on its device."""
+        h = self._live()
+        tdev = scalar32.device if _is_torch(scalar32) else None
+        sc = np.ascontiguousarray(scalar32.detach().cpu().numpy() if tdev is not None else scalar32)
+        terms = _rows(sc)
+        if terms % self.m:
+            raise ValueError("FixedBases.msm: the number of scalars must be a multiple of m = %d" % self.m)
+        n = terms // self.m
+        _check(sc, ENC, terms, "FixedBases.msm scalars")
+        enc = np.empty((n, 32), np.uint8)
+        xyzt = np.empty((n, 16), np.uint64) if elements else None
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _native.check(self._lib.d377_batch_fixed_msm(self.ctx._h, h, p(sc), ctypes.c_size_t(n), p(enc), p(xyzt) if elements else None))
+        if tdev is not None:
+            import torch
+            enc = torch.from_numpy(enc).to(tdev)
+            if elements:
+                xyzt = torch.from_numpy(xyzt.view(np.int64)).to(tdev)
+        return (enc, xyzt) if elements else enc
+
+    def vartime_multiscalar_mul(self, scalars):
+        """The sums' Encodings for an Fr batch (or [n * m, 32] array) of n x m scalars, term-major within a sum."""
+        return Encoding(self.msm(scalars.data if isinstance(scalars, _Bytes32) else scalars), self.ctx)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            _native.check(self._lib.d377_fixed_bases_destroy(self.ctx._h, self._h))
+            self._h = 0
+            fixed = getattr(self.ctx, "_fixed", None)
+            if fixed is not None:
+                fixed.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 _default = None

@@ -301,6 +301,39 @@ int d377_batch_msm_small(d377_ctx* ctx, const uint64_t* xyzt, const uint8_t* sca
 int d377_batch_msm_small_encoded(d377_ctx* ctx, const uint8_t* enc32, const uint8_t* scalar32, size_t m, size_t n,
                                  uint8_t* enc32_out, uint64_t* xyzt_out, uint8_t* status);
 
+/* Fixed-base combs for caller-chosen points, and many sums over them.  The reference reaches this through arkworks:
+ * Element implements ScalarMul / VariableBaseMSM / CurveGroup (src/ark_curve/element.rs:22-38), so ark-ec's FixedBase
+ * window tables work on any Element -- a Pedersen commitment v G + r H, a value commitment's asset and blinding generators.
+ *
+ * d377_fixed_bases_create registers 1 <= m <= D377_FIXED_BASES_MAX bases (m x 16 u64 Element records, read as the extended
+ * coordinates they are, T Z = X Y; a record with Z = 0 counts as the identity) and builds one comb per base on every device
+ * of the context: window i of base j holds c * 2^(comb_bits i) * B_j for 0 <= c <= 2^(comb_bits - 1).  comb_bits: 8, 12,
+ * 16 or 18 (0 = 16); per base 0.53 MB / 5.5 MB / 67 MB / 235 MB of HBM and 32 / 21 / 16 / 14 mixed additions per sum.
+ * m, comb_bits and the pointers are checked before any device is touched (D377_ERR_ARG, the message names the argument);
+ * tables that do not fit fail with D377_ERR_HIP and leave nothing allocated.  The context's own generator comb
+ * (d377_ctx_create_ex) is independent of these.
+ *
+ * d377_batch_fixed_msm computes n sums, enc32_out[i] = the canonical Encoding of
+ *     scalar[i m] * B_0 + ... + scalar[i m + m - 1] * B_{m-1}
+ * (scalars term-major within a sum, n x m 32-byte strings, any 32 bytes, reduced mod r) and, if xyzt_out != NULL, the
+ * sums as Element records (n x 16 u64, some extended representative: equal under d377_batch_eq, same encoding).  Any
+ * representative of a base gives the same encodings, one that differs by a torsion point the encoding quotients away
+ * included.  m = 1 is a fixed-base multiplication by B_0.  A multi-GPU context slices the SUMS over its devices.
+ * Host pointers only: a device-pointer form is not offered (a Python torch tensor is staged through host memory).
+ *
+ * Handles: a handle is a positive integer that names one registration within its context (never reused by that
+ * context); every call takes the context and the handle, and a handle that was destroyed, or never created there, is
+ * refused with D377_ERR_ARG.  Threads and lifetime: calls on one handle, or on several handles of one context, may come
+ * from several host threads; they are serialised by the context's mutex like every host-pointer call.  Handles are
+ * destroyed before their context; d377_ctx_destroy releases the tables of any handle still alive.  The C++ and Python
+ * wrappers keep that order themselves.  d377_fixed_bases_info reports m, the comb width and the table bytes per device. */
+#define D377_FIXED_BASES_MAX 64
+int d377_fixed_bases_create(d377_ctx* ctx, const uint64_t* xyzt, size_t m, int comb_bits, int64_t* handle_out);
+int d377_fixed_bases_info(d377_ctx* ctx, int64_t handle, uint64_t* m, int* comb_bits, uint64_t* table_bytes_per_device);
+int d377_fixed_bases_destroy(d377_ctx* ctx, int64_t handle);
+int d377_batch_fixed_msm(d377_ctx* ctx, int64_t handle, const uint8_t* scalar32, size_t n, uint8_t* enc32_out,
+                         uint64_t* xyzt_out);
+
 /* Fq field operations on in-memory elements (4 Montgomery u64 limbs, R = 2^256, fully reduced), the
  * unit everything above is built from             src/fields/fq/u64/wrapper.rs:99-132, fq/ops.rs
  * op: D377_FQ_ADD / SUB / MUL (binary, b != NULL) and D377_FQ_SQUARE / NEG / INVERSE (unary, b NULL).

@@ -125,6 +125,50 @@ impl Drop for GpuContext {
     }
 }
 
+/// Fixed-base combs for caller-chosen points (d377_fixed_bases_create): ark-ec's `FixedBase` window tables over any
+/// `Element` (src/ark_curve/element.rs:22-38), one comb per base on every device of the context.  It borrows its
+/// `GpuContext`, so the borrow checker keeps it from outliving the context; `Drop` releases the tables.
+pub struct FixedBases<'a> {
+    ctx: &'a GpuContext,
+    handle: i64,
+    m: usize,
+}
+impl<'a> FixedBases<'a> {
+    /// 1..=64 bases; `comb_bits` 8, 12, 16 or 18 (0.53 / 5.5 / 67 / 235 MB per base and device).
+    pub fn new(ctx: &'a GpuContext, bases: &[Element], comb_bits: i32) -> Result<Self, GpuError> {
+        let xyzt = elements_to_xyzt(bases);
+        let mut handle = 0i64;
+        check(unsafe { ffi::d377_fixed_bases_create(ctx.0, xyzt.as_ptr(), bases.len(), comb_bits, &mut handle) })?;
+        Ok(Self { ctx, handle, m: bases.len() })
+    }
+    /// (m, comb width in bits, table bytes per device)
+    pub fn info(&self) -> Result<(u64, i32, u64), GpuError> {
+        let (mut m, mut bits, mut bytes) = (0u64, 0i32, 0u64);
+        check(unsafe { ffi::d377_fixed_bases_info(self.ctx.0, self.handle, &mut m, &mut bits, &mut bytes) })?;
+        Ok((m, bits, bytes))
+    }
+    /// n sums, sum i = scalars[i m] * B_0 + ... + scalars[i m + m - 1] * B_{m-1} (term-major): their Encodings and
+    /// the sums as Elements, which the same pass computes.
+    pub fn vartime_multiscalar_mul(&self, scalars: &[Fr]) -> Result<(Vec<Encoding>, Vec<Element>), GpuError> {
+        assert!(scalars.len() % self.m == 0);
+        let n = scalars.len() / self.m;
+        let bytes = pack32(scalars, |k| k.to_bytes());
+        let mut enc = vec![Encoding([0u8; 32]); n];
+        let mut out = vec![0u64; 16 * n];
+        check(unsafe {
+            ffi::d377_batch_fixed_msm(self.ctx.0, self.handle, bytes.as_ptr(), n, enc.as_mut_ptr() as *mut u8, out.as_mut_ptr())
+        })?;
+        Ok((enc, out.chunks_exact(16).map(element_from_xyzt).collect()))
+    }
+}
+impl Drop for FixedBases<'_> {
+    fn drop(&mut self) {
+        unsafe {
+            ffi::d377_fixed_bases_destroy(self.ctx.0, self.handle);
+        }
+    }
+}
+
 // ---- record conversions ------------------------------------------------------------------------
 // Encoding(pub [u8; 32]) is a newtype over the bytes, so &[Encoding] is already a packed [n][32] array.
 fn enc_ptr(e: &[Encoding]) -> *const u8 {

@@ -11,7 +11,7 @@ import subprocess
 import sys
 
 ARGS = sys.argv[1:]
-UNITS = ("d377", "msm", "codec_chunked", "batch_msm")
+UNITS = ("d377", "msm", "codec_chunked", "batch_msm", "fixed_bases")
 if ARGS and ARGS[0] == "--units":
     UNITS = tuple(ARGS[1].split(","))
     ARGS = ARGS[2:]
