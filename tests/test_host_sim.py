@@ -386,6 +386,50 @@ def _val(limbs):
     return sum(int(v) << (29 * i) for i, v in enumerate(limbs))
 
 
+LAZY = (1 << 30) + 16
+CARRIED = (1 << 29) + 8
+WIDE = (1 << 30) + (1 << 29) + 16           # fe_sub_nc output: carried + a 2^30 offset digit
+TOP = 1 << 24                               # limb 8 of a value around 13 q
+PAIRINGS = [(LAZY, LAZY), (WIDE, CARRIED), (CARRIED, WIDE), (LAZY, CARRIED), (CARRIED, CARRIED)]
+
+
+def _adversarial_cases():
+    """The operand rows of test_limb_bounds_adversarial (tests/test_field_streams.py runs the same rows on the GPU): for
+    each pairing of PAIRINGS the all-extreme row with top limb 2^24, the same with top limb 0, and 200 seeded mixtures."""
+    lazy, carried, wide, top = LAZY, CARRIED, WIDE, TOP
+    rng = np.random.default_rng(15)
+    cases = []
+    for la, lb in PAIRINGS:
+        cases.append(([la] * 8 + [top], [lb] * 8 + [top]))
+        cases.append(([la] * 8 + [0], [lb] * 8 + [0]))
+        for _ in range(200):                # random mixtures of extreme and random limbs
+            a = [la if rng.random() < 0.7 else int(rng.integers(0, la + 1)) for _ in range(8)] + [int(rng.integers(0, top))]
+            b = [lb if rng.random() < 0.7 else int(rng.integers(0, lb + 1)) for _ in range(8)] + [int(rng.integers(0, top))]
+            cases.append((a, b))
+    a = np.array([c[0] for c in cases], dtype=np.uint32)
+    b = np.array([c[1] for c in cases], dtype=np.uint32)
+    return a, b
+
+
+def _squarer_rows(a, scale):
+    """The rows of _adversarial_cases a squarer may take: largest limb <= lazy, <= carried for 2 a^2."""
+    return [i for i in range(a.shape[0]) if max(int(x) for x in a[i][:8]) <= (LAZY if scale == 1 else CARRIED)]
+
+
+def _adversarial_linear_rows():
+    """(sub_a, sub_b), (nc_a, nc_b), reps: the subtraction, no-carry subtraction and canonicalisation rows."""
+    lazy, carried, top = LAZY, CARRIED, TOP
+    sub_a = np.array([[lazy] * 8 + [top]] * 4 + [[0] * 9] * 4, dtype=np.uint32)
+    sub_b = np.array([[lazy] * 8 + [0], [0] * 9, [carried] * 8 + [1 << 21], [lazy] * 8 + [(1 << 24)]] * 2, dtype=np.uint32)
+    nc_a = np.array([[carried] * 8 + [top], [0] * 9, [carried] * 8 + [0], [5] * 9], dtype=np.uint32)
+    nc_b = np.array([[carried] * 8 + [1 << 24], [carried] * 8 + [1 << 24], [0] * 9, [carried] * 8 + [7]], dtype=np.uint32)
+    reps = []
+    for k in range(0, 12):
+        v = k * Q
+        reps.append([(v >> (29 * i)) & ((1 << 29) - 1) for i in range(8)] + [v >> 232])
+    return (sub_a, sub_b), (nc_a, nc_b), np.array(reps, dtype=np.uint32)
+
+
 def test_limb_bounds_adversarial(sim):
     """fq29.hpp's representation contract at its edges: every limb at the documented maximum
     (lazy = 2^30 + 16 on both sides; carried + 2^30 against a carried operand), so that each 64-bit
@@ -395,21 +439,7 @@ def test_limb_bounds_adversarial(sim):
     (relaxed) or + q (strict)."""
     R = 1 << 261
     Rinv = pow(R, -1, Q)
-    lazy = (1 << 30) + 16
-    carried = (1 << 29) + 8
-    wide = (1 << 30) + (1 << 29) + 16        # fe_sub_nc output: carried + a 2^30 offset digit
-    top = (1 << 24)                         # limb 8 of a value around 13 q
-    rng = np.random.default_rng(15)
-    cases = []
-    for la, lb in [(lazy, lazy), (wide, carried), (carried, wide), (lazy, carried), (carried, carried)]:
-        cases.append(([la] * 8 + [top], [lb] * 8 + [top]))
-        cases.append(([la] * 8 + [0], [lb] * 8 + [0]))
-        for _ in range(200):                # random mixtures of extreme and random limbs
-            a = [la if rng.random() < 0.7 else int(rng.integers(0, la + 1)) for _ in range(8)] + [int(rng.integers(0, top))]
-            b = [lb if rng.random() < 0.7 else int(rng.integers(0, lb + 1)) for _ in range(8)] + [int(rng.integers(0, top))]
-            cases.append((a, b))
-    a = np.array([c[0] for c in cases], dtype=np.uint32)
-    b = np.array([c[1] for c in cases], dtype=np.uint32)
+    a, b = _adversarial_cases()
     n = a.shape[0]
     out = np.zeros((n, 9), np.uint32)
     for mode, slack in ((0, 8), (1, 1)):
@@ -420,7 +450,7 @@ def test_limb_bounds_adversarial(sim):
             assert vr < va * vb // R + slack * Q + 1
             assert all(int(x) < (1 << 29) for x in out[i][:8])
     for mode, slack, scale in ((2, 8, 1), (3, 1, 1), (4, 8, 2)):
-        sel = [i for i in range(n) if max(int(x) for x in a[i][:8]) <= (lazy if scale == 1 else carried)]
+        sel = _squarer_rows(a, scale)
         aa = np.ascontiguousarray(a[sel])
         oo = np.zeros((len(sel), 9), np.uint32)
         sim.sim_raw_mul(mode, _p(aa), _p(aa), n_(len(sel)), _p(oo))
@@ -429,9 +459,8 @@ def test_limb_bounds_adversarial(sim):
             assert vr % Q == scale * va * va * Rinv % Q, (mode, i)
             assert vr < scale * va * va // R + slack * Q + 1
             assert all(int(x) < (1 << 29) for x in oo[i][:8])
+    (sub_a, sub_b), (nc_a, nc_b), reps = _adversarial_linear_rows()
     # subtraction: minuend lazy, subtrahend lazy with value < 31q -> exact value a - b + 32q, carried limbs
-    sub_a = np.array([[lazy] * 8 + [top]] * 4 + [[0] * 9] * 4, dtype=np.uint32)
-    sub_b = np.array([[lazy] * 8 + [0], [0] * 9, [carried] * 8 + [1 << 21], [lazy] * 8 + [(1 << 24)]] * 2, dtype=np.uint32)
     out = np.zeros((8, 9), np.uint32)
     sim.sim_raw_sub(0, _p(sub_a), _p(sub_b), n_(8), _p(out))
     for i in range(8):
@@ -439,19 +468,12 @@ def test_limb_bounds_adversarial(sim):
         assert _val(out[i]) == _val(sub_a[i]) - _val(sub_b[i]) + 32 * Q
         assert all(int(x) < (1 << 29) + 8 for x in out[i][:8])
     # no-carry subtraction: carried subtrahend, result = a - b + 16q limb by limb, limbs < a's + 2^30 + 8
-    nc_a = np.array([[carried] * 8 + [top], [0] * 9, [carried] * 8 + [0], [5] * 9], dtype=np.uint32)
-    nc_b = np.array([[carried] * 8 + [1 << 24], [carried] * 8 + [1 << 24], [0] * 9, [carried] * 8 + [7]], dtype=np.uint32)
     out = np.zeros((4, 9), np.uint32)
     sim.sim_raw_sub(1, _p(nc_a), _p(nc_b), n_(4), _p(out))
     for i in range(4):
         assert _val(out[i]) == _val(nc_a[i]) - _val(nc_b[i]) + 16 * Q
         assert all(int(x) < int(y) + (1 << 30) + 8 for x, y in zip(out[i][:8], nc_a[i][:8]))
     # canonicalisation of the representatives of zero and of small multiples of q (relaxed products reach 8q+)
-    reps = []
-    for k in range(0, 12):
-        v = k * Q
-        reps.append([(v >> (29 * i)) & ((1 << 29) - 1) for i in range(8)] + [v >> 232])
-    reps = np.array(reps, dtype=np.uint32)
     out = np.zeros((12, 9), np.uint32)
     sim.sim_raw_canon(_p(reps), n_(12), _p(out))
     assert not out.any()

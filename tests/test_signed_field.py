@@ -105,16 +105,23 @@ def _operands(rng, n, wide):
     return rows
 
 
-@pytest.mark.parametrize("kind", ["mul", "sqr", "sqr2x"])
-def test_signed_products(ssim, kind):
-    """Signed products at the contract's extreme limbs: exactly the stream's result, congruent to (s) a b / R, limbs 0..7
-    in [0, 2^29), value in (s a b / R - q, s a b / R], every partial column sum inside +-2^63."""
+def _product_rows(kind):
+    """The operand rows of test_signed_products (tests/test_field_streams.py runs the same rows on the GPU): 600 seeded rows
+    and the 49 extreme mixes, at the widths the kind's contract allows."""
     rng = np.random.default_rng({"mul": 1, "sqr": 2, "sqr2x": 3}[kind])
     lazy = (1 << 30) + (1 << 29) + 16            # a wide (lazy) operand times a carried one; a square of limbs below
     carried = (1 << 29) + 8                      # 2^30 - 2^27 (a sum of two products); twice the square of a carried one
     a_rows = _operands(rng, 600, {"mul": lazy, "sqr": (1 << 30) - (1 << 27), "sqr2x": carried}[kind])
     b_rows = _operands(rng, len(a_rows), carried)
     rng.shuffle(b_rows)
+    return a_rows, b_rows
+
+
+@pytest.mark.parametrize("kind", ["mul", "sqr", "sqr2x"])
+def test_signed_products(ssim, kind):
+    """Signed products at the contract's extreme limbs: exactly the stream's result, congruent to (s) a b / R, limbs 0..7
+    in [0, 2^29), value in (s a b / R - q, s a b / R], every partial column sum inside +-2^63."""
+    a_rows, b_rows = _product_rows(kind)
     a = np.array(a_rows, np.int32)
     b = np.array(b_rows, np.int32)
     r = np.zeros_like(a)
@@ -131,22 +138,29 @@ def test_signed_products(ssim, kind):
         assert t - Q * (1 << 261) < v * (1 << 261) <= t
 
 
-def test_signed_linear_and_conversion(ssim):
-    """fe_sub without offset, the arithmetic-shift carry pass (value kept) and fes -> fe (+2q, carried, same residue)."""
+def _linear_rows():
+    """The rows of test_signed_linear_and_conversion: (a, b) for fe_sub and fe_carry, p for fes -> fe."""
     rng = np.random.default_rng(4)
     n = 400
     a = rng.integers(-(1 << 30), 1 << 30, (n, 9)).astype(np.int32)
     b = rng.integers(-(1 << 30), 1 << 30, (n, 9)).astype(np.int32)
+    # a product-form input (limbs 0..7 in [0, 2^29), signed top), value above -2q + 2^233
+    p = rng.integers(0, 1 << 29, (n, 9)).astype(np.int32)
+    p[:, 8] = rng.integers(-2 * QL[8] + 2, 1 << 19, n)
+    p[0, :8], p[0, 8] = 0, -(2 * QL[8]) + 2
+    return a, b, p
+
+
+def test_signed_linear_and_conversion(ssim):
+    """fe_sub without offset, the arithmetic-shift carry pass (value kept) and fes -> fe (+2q, carried, same residue)."""
+    a, b, p = _linear_rows()
+    n = len(a)
     r = np.zeros_like(a)
     ssim.sims_field_op(4, _p(a), _p(b), ctypes.c_size_t(n), _p(r))
     assert (r.astype(np.int64) == a.astype(np.int64) - b).all()
     ssim.sims_field_op(3, _p(a), _p(b), ctypes.c_size_t(n), _p(r))
     for x, z in zip(a.tolist(), r.tolist()):
         assert _value(z) == _value(x) and all(-2 <= l < (1 << 29) + 2 for l in z[:8])
-    # a product-form input (limbs 0..7 in [0, 2^29), signed top), value above -2q + 2^233
-    p = rng.integers(0, 1 << 29, (n, 9)).astype(np.int32)
-    p[:, 8] = rng.integers(-2 * QL[8] + 2, 1 << 19, n)
-    p[0, :8], p[0, 8] = 0, -(2 * QL[8]) + 2
     ssim.sims_field_op(5, _p(p), _p(b), ctypes.c_size_t(n), _p(r))
     for x, z in zip(p.tolist(), r.astype(np.uint32).tolist()):
         assert _value(z) == _value(x) + 2 * Q and all(l < (1 << 29) + 8 for l in z[:8])
