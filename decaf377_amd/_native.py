@@ -41,6 +41,7 @@ EXPORTS = [
     "d377_ctx_create_ex", "d377_ctx_comb_info",
     "d377_batch_msm_small", "d377_batch_msm_small_encoded", "d377_batch_msm_small_dev", "d377_batch_msm_small_encoded_dev",
     "d377_fixed_bases_create", "d377_fixed_bases_info", "d377_fixed_bases_destroy", "d377_batch_fixed_msm",
+    "d377_batch_fixed_msm_indexed",
 ]
 
 
@@ -194,7 +195,9 @@ def load():
     lib.d377_fixed_bases_info.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_uint64)]
     lib.d377_fixed_bases_destroy.argtypes = [vp, ctypes.c_int64]
     lib.d377_batch_fixed_msm.argtypes = [vp, ctypes.c_int64, vp, sz, vp, vp]
-    for name in ("d377_fixed_bases_create", "d377_fixed_bases_info", "d377_fixed_bases_destroy", "d377_batch_fixed_msm"):
+    lib.d377_batch_fixed_msm_indexed.argtypes = [vp, ctypes.c_int64, vp, vp, sz, sz, vp, vp]
+    for name in ("d377_fixed_bases_create", "d377_fixed_bases_info", "d377_fixed_bases_destroy", "d377_batch_fixed_msm",
+                 "d377_batch_fixed_msm_indexed"):
         getattr(lib, name).restype = i32
     _lib = lib
     return lib

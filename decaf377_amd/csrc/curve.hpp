@@ -1194,6 +1194,22 @@ D377_HD ge ge_fixed_msm_w8(int m, KLoad&& kload, const FTab& ftab, bool want_t =
   }
   return r;
 }
+// The sum whose terms name their bases (d377_batch_fixed_msm_indexed): term j walks comb tload(j, k) with the scalar
+// tload leaves in k -- the walk above, whose kload(j, k) comes before the first ftab.load(j, ...) of term j, so the entry
+// fetched across the boundary between two terms is already the next term's digit in the next term's comb.  The comb is
+// asked for once per term.  An absent term is tload's business: scalar 0 on comb 0 walks entry 0 of every window, the
+// identity record, and the control flow stays the dense walk's.
+template <class FTab>
+struct FbIndexedTabs {
+  const FTab& tabs;
+  int comb;                                            // the comb of the term whose entries are being fetched
+  D377_HD gea load(int, int i, int c, bool swap) const { return tabs.load(comb, i, c, swap); }
+};
+template <int BITS, class FTab, class TLoad>
+D377_HD ge ge_fixed_msm_indexed_w8(int t, TLoad&& tload, const FTab& ftab, bool want_t = true) {
+  FbIndexedTabs<FTab> it{ftab, 0};
+  return ge_fixed_msm_w8<BITS>(t, [&](int j, uint32_t k[8]) { it.comb = tload(j, k); }, it, want_t);
+}
 
 // generic x^e for a 256-bit exponent given as 8 words (init kernels only: inversion by q - 2)
 D377_HD fe fe_pow_words(const fe& x, const uint32_t (&e)[8]) {

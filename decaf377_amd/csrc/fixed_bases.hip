@@ -2,6 +2,8 @@
 //   d377_fixed_bases_create   one comb per base on every device (fixed_comb.hpp: k_fb_window_bases, then ONE k_init_fbase
 //                             launch over the m x W windows of all bases)
 //   d377_batch_fixed_msm      out[i] = sum_j scalar[i m + j] * B_j, one lane per sum
+//   d377_batch_fixed_msm_indexed   out[i] = sum_{j < t} scalar[i t + j] * B_{base_index[i t + j]}: the same walk, each term in
+//                             the comb it names (curve.hpp: ge_fixed_msm_indexed_w8); -1 = the term is absent
 //
 // The sum is k_scalar_mul_base's walk widened to m combs (curve.hpp: ge_fixed_msm_w8): each base's scalar is reduced and
 // halved, its W signed digits pick one entry per window, and all m x W mixed additions go into ONE accumulator -- no
@@ -73,6 +75,41 @@ k_fixed_msm_lane(SqrtTables T, const uint32_t* tabs, const uint8_t* scalar32, in
   D377_DCB_END();
 }
 
+// The sum whose terms name their bases: term p of lane i walks comb base_index[i t + p].  The lanes of a wave gather from
+// different combs; their control flow is the dense kernel's.  An absent term (-1) walks scalar 0 on comb 0, entry 0 of every
+// window, the identity record.  The host has refused every other index outside 0 .. m-1 before the launch
+// (d377_batch_fixed_msm_indexed); the unsigned compare below treats one as absent all the same, so no index can address past
+// the m combs.
+template <int BITS>
+__global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD)
+k_fixed_msm_indexed_lane(SqrtTables T, const uint32_t* tabs, const int* base_index, const uint8_t* scalar32, int m, int t, size_t n,
+                         uint8_t* out32, uint64_t* xyzt_out, DcbScratch dcb) {
+  __shared__ uint32_t lds_pow_[1];                                 // (no square root here: residency is set by the launch's padding)
+  LdsPowTab pt;
+  pt.col = lds_pow_;
+  D377_DCB_BEGIN(out32);
+  const CombTabs<BITS> ft{tabs};
+  dcb_rounds<0, true>(n, io, pt,
+    [&](size_t, int) {},
+    [&](size_t i, int j, const uint32_t (*)[8], bool) {
+      const size_t first = i * (size_t)t;
+      const ge r = ge_fixed_msm_indexed_w8<BITS>(t, [&](int p, uint32_t k[8]) -> int {
+        const int b = base_index[first + (size_t)p];               // once per term
+        load32(scalar32, first + (size_t)p, k);
+        fr_reduce_words(k);
+        fr_half_words(k);
+        const uint32_t keep = (uint32_t)b < (uint32_t)m ? ~0u : 0u;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) k[q] &= keep;
+        return (int)((uint32_t)b & keep);
+      }, ft, DCB_WANT_T);
+      D377_INVARIANT(T, r, true);
+      if (xyzt_out) store_ge_mont256(xyzt_out, i, ge_double_fast(r, true));   // the sum itself is the double
+      dcb_put(io, j, ge_dcb_from_half(r, false));
+    });
+  D377_DCB_END();
+}
+
 // ------------------------------------------------------------------------------ host side ---
 // The comb widths a handle may ask for; f(std::integral_constant<int, BITS>) runs with the kernels of that width.
 int width_slot(int bits) { return bits == 8 ? 0 : bits == 12 ? 1 : bits == 16 ? 2 : bits == 18 ? 3 : -1; }
@@ -89,14 +126,19 @@ int with_width(int bits, F&& f) {
 template <int BITS>
 size_t comb_bytes() { return (size_t)FbShape<BITS>::windows * FbShape<BITS>::entries * FBW_ENTRY_WORDS * sizeof(uint32_t); }
 
-// Residency of the lane kernel against the lane sets (as d377_ctx_create checks the kernels of d377.hip): at most
+// Residency of the two lane kernels against the lane sets (as d377_ctx_create checks the kernels of d377.hip): at most
 // WAVES_PER_SIMD workgroups per CU, padded with dynamic LDS where registers alone would let more in.  Once per device and
 // width, by d377_fixed_bases_create; the caller holds ctx->mu.
+int check_residency_of(const void* fn, const char* name, int bits, int& lds);
 template <int BITS>
 int check_residency_fx(DeviceState& d) {
-  int& lds = d.fx_lds[width_slot(BITS)];
+  int rc = check_residency_of(reinterpret_cast<const void*>(k_fixed_msm_lane<BITS>), "k_fixed_msm_lane", BITS, d.fx_lds[width_slot(BITS)]);
+  if (rc) return rc;
+  return check_residency_of(reinterpret_cast<const void*>(k_fixed_msm_indexed_lane<BITS>), "k_fixed_msm_indexed_lane", BITS,
+                            d.fxi_lds[width_slot(BITS)]);
+}
+int check_residency_of(const void* fn, const char* name, int bits, int& lds) {
   if (lds >= 0) return D377_OK;
-  const void* fn = reinterpret_cast<const void*>(k_fixed_msm_lane<BITS>);
   int nb = 0;
   HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, 0));
   int pad = 0;
@@ -106,9 +148,9 @@ int check_residency_fx(DeviceState& d) {
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, (size_t)pad));
   }
   if (getenv("D377_DEBUG_RESIDENCY"))
-    fprintf(stderr, "d377: k_fixed_msm_lane<%d>: %d workgroups per CU with %d bytes of LDS padding\n", BITS, nb, pad);
+    fprintf(stderr, "d377: %s<%d>: %d workgroups per CU with %d bytes of LDS padding\n", name, bits, nb, pad);
   if (nb < 1 || nb > WAVES_PER_SIMD)
-    return fail(D377_ERR_INIT, "residency of %s does not match the lane sets of the scratch areas", "k_fixed_msm_lane");
+    return fail(D377_ERR_INIT, "residency of %s does not match the lane sets of the scratch areas", name);
   lds = pad;
   return D377_OK;
 }
@@ -158,12 +200,13 @@ int build_on(DeviceState& d, const uint64_t* xyzt, size_t m, uint32_t** out) {
   return D377_OK;
 }
 
-// everything on device pointers, enqueued on `s`; the caller holds ctx->mu
-int fixed_msm_launch(DeviceState& d, hipStream_t s, const FixedBases& fb, const uint32_t* tab, const uint8_t* scalars, size_t n,
-                     uint8_t* out32, uint64_t* xyzt_out) {
+// everything on device pointers, enqueued on `s`; the caller holds ctx->mu.  index == null: the dense sums over all m bases;
+// otherwise n x t indices the host has checked, and t terms per sum.
+int fixed_msm_launch(DeviceState& d, hipStream_t s, const FixedBases& fb, const uint32_t* tab, const int* index, size_t t,
+                     const uint8_t* scalars, size_t n, uint8_t* out32, uint64_t* xyzt_out) {
   if (n == 0) return D377_OK;
-  const int lds = d.fx_lds[width_slot(fb.bits)];
-  if (lds < 0) return fail(D377_ERR_INIT, "%s", "k_fixed_msm_lane: residency not checked on this device");
+  const int lds = index ? d.fxi_lds[width_slot(fb.bits)] : d.fx_lds[width_slot(fb.bits)];
+  if (lds < 0) return fail(D377_ERR_INIT, "%s: residency not checked on this device", index ? "k_fixed_msm_indexed_lane" : "k_fixed_msm_lane");
   GuardScope vb{d.vb_guard, s};                              // the lane-set areas: queue behind their last user
   int rc;
   if ((rc = vb.acquire())) return rc;
@@ -173,30 +216,37 @@ int fixed_msm_launch(DeviceState& d, hipStream_t s, const FixedBases& fb, const 
   dcb.prio = c.nchunks <= 2 * places ? 1 : 0;               // as d377.hip's chunks_of
   const SqrtTables T = d.tables();
   if ((rc = with_width(fb.bits, [&](auto b) -> int {
-         hipLaunchKernelGGL(k_fixed_msm_lane<decltype(b)::value>, dim3((unsigned)c.nchunks), dim3(BLOCK), lds, s, T, tab, scalars,
-                            (int)fb.m, n, out32, xyzt_out, dcb);
+         if (index)
+           hipLaunchKernelGGL(k_fixed_msm_indexed_lane<decltype(b)::value>, dim3((unsigned)c.nchunks), dim3(BLOCK), lds, s, T, tab,
+                              index, scalars, (int)fb.m, (int)t, n, out32, xyzt_out, dcb);
+         else
+           hipLaunchKernelGGL(k_fixed_msm_lane<decltype(b)::value>, dim3((unsigned)c.nchunks), dim3(BLOCK), lds, s, T, tab, scalars,
+                              (int)fb.m, n, out32, xyzt_out, dcb);
          return D377_OK; }))) return rc;
   HIP_TRY(hipGetLastError());
   return vb.finish();
 }
 
-// one device's slice of a host batch: copies in, kernel, copies out, synchronised
-int fixed_msm_one(DeviceState& d, const FixedBases& fb, const uint32_t* tab, const uint8_t* scalars, size_t n, uint8_t* out32,
-                  uint64_t* xyzt_out) {
+// one device's slice of a host batch: copies in, kernel, copies out, synchronised.  index == null: dense, t = m; otherwise the
+// slice's n x t indices, staged behind its scalars (n t x 32 bytes: 16-byte aligned).
+int fixed_msm_one(DeviceState& d, const FixedBases& fb, const uint32_t* tab, const int* index, size_t t, const uint8_t* scalars,
+                  size_t n, uint8_t* out32, uint64_t* xyzt_out) {
   if (n == 0) return D377_OK;
   HIP_TRY(hipSetDevice(d.id));
   int rc = D377_OK;
   SyncOnError guard{&rc, d.id, d.stream, nullptr};
   auto body = [&]() -> int {
-    const size_t terms = n * fb.m;
+    const size_t terms = n * t;
     int r;
-    if ((r = ensure(d, 1, terms * 32))) return r;
+    if ((r = ensure(d, 1, terms * 32 + (index ? terms * sizeof(int) : 0)))) return r;
     if ((r = ensure(d, 2, n * (xyzt_out ? 32 + 128 : 32)))) return r;      // the Encodings, then the Element records
     StarveCheck starve{d, d.stream};
     if ((r = starve.before())) return r;
     HIP_TRY(hipMemcpyAsync(d.buf[1], scalars, terms * 32, hipMemcpyHostToDevice, d.stream));
+    const int* index_dev = index ? reinterpret_cast<const int*>(d.buf[1] + terms * 32) : nullptr;
+    if (index) HIP_TRY(hipMemcpyAsync(d.buf[1] + terms * 32, index, terms * sizeof(int), hipMemcpyHostToDevice, d.stream));
     uint64_t* xyzt_dev = xyzt_out ? reinterpret_cast<uint64_t*>(d.buf[2] + n * 32) : nullptr;
-    if ((r = fixed_msm_launch(d, d.stream, fb, tab, d.buf[1], n, d.buf[2], xyzt_dev))) return r;
+    if ((r = fixed_msm_launch(d, d.stream, fb, tab, index_dev, t, d.buf[1], n, d.buf[2], xyzt_dev))) return r;
     HIP_TRY(hipMemcpyAsync(out32, d.buf[2], n * 32, hipMemcpyDeviceToHost, d.stream));
     if (xyzt_out) HIP_TRY(hipMemcpyAsync(xyzt_out, xyzt_dev, n * 128, hipMemcpyDeviceToHost, d.stream));
     if ((r = starve.after())) return r;
@@ -205,6 +255,35 @@ int fixed_msm_one(DeviceState& d, const FixedBases& fb, const uint32_t* tab, con
   };
   rc = body();
   return rc;
+}
+
+// n sums in contiguous slices over the context's devices, one host thread per device (as batch_msm.hip); t terms per sum,
+// index == null for the dense sums.  Caller holds ctx->mu.
+int fixed_msm_sliced(d377_ctx* ctx, const FixedBases& fb, const int* index, size_t t, const uint8_t* scalar32, size_t n,
+                     uint8_t* enc32_out, uint64_t* xyzt_out) {
+  if (n == 0) return D377_OK;
+  const size_t nd = ctx->devs.size();
+  if (nd == 1) return fixed_msm_one(ctx->devs[0], fb, fb.tab[0], index, t, scalar32, n, enc32_out, xyzt_out);
+  const size_t per = (n + nd - 1) / nd;
+  std::vector<int> rcs(nd, D377_OK);
+  std::vector<std::string> errs(nd);
+  std::vector<std::thread> workers;
+  const int delay = debug_device_delay_ms();
+  for (size_t k = 0; k < nd; ++k) {
+    const size_t lo = per * k;
+    if (lo >= n) break;
+    const size_t cnt = (lo + per <= n) ? per : n - lo;
+    workers.emplace_back([&, k, lo, cnt]() {
+      if (delay > 0) std::this_thread::sleep_for(std::chrono::milliseconds(delay));
+      rcs[k] = fixed_msm_one(ctx->devs[k], fb, fb.tab[k], index ? index + lo * t : nullptr, t, scalar32 + lo * t * 32, cnt,
+                             enc32_out + lo * 32, xyzt_out ? xyzt_out + lo * 16 : nullptr);
+      if (rcs[k] != D377_OK) errs[k] = d377_g_err;
+    });
+  }
+  for (auto& w : workers) w.join();
+  for (size_t k = 0; k < nd; ++k)
+    if (rcs[k] != D377_OK) return fail(rcs[k], "%s", errs[k].c_str());
+  return D377_OK;
 }
 
 // frees a registration's tables (every device); caller holds ctx->mu or is destroying the context
@@ -308,29 +387,35 @@ int d377_batch_fixed_msm(d377_ctx* ctx, int64_t handle, const uint8_t* scalar32,
   std::lock_guard<std::mutex> lock(ctx->mu);
   const FixedBases* fb = find(ctx, handle);
   if (!fb) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_msm: handle is not a live registration of this context");
-  if (n == 0) return D377_OK;
-  const size_t nd = ctx->devs.size(), m = fb->m;
-  if (nd == 1) return fixed_msm_one(ctx->devs[0], *fb, fb->tab[0], scalar32, n, enc32_out, xyzt_out);
-  const size_t per = (n + nd - 1) / nd;
-  std::vector<int> rcs(nd, D377_OK);
-  std::vector<std::string> errs(nd);
-  std::vector<std::thread> workers;
-  const int delay = debug_device_delay_ms();
-  for (size_t k = 0; k < nd; ++k) {
-    const size_t lo = per * k;
-    if (lo >= n) break;
-    const size_t cnt = (lo + per <= n) ? per : n - lo;
-    workers.emplace_back([&, k, lo, cnt]() {
-      if (delay > 0) std::this_thread::sleep_for(std::chrono::milliseconds(delay));
-      rcs[k] = fixed_msm_one(ctx->devs[k], *fb, fb->tab[k], scalar32 + lo * m * 32, cnt, enc32_out + lo * 32,
-                             xyzt_out ? xyzt_out + lo * 16 : nullptr);
-      if (rcs[k] != D377_OK) errs[k] = d377_g_err;
-    });
+  return fixed_msm_sliced(ctx, *fb, nullptr, fb->m, scalar32, n, enc32_out, xyzt_out);
+}
+
+// the same slices; the index rows and scalar rows of a sum travel with it
+int d377_batch_fixed_msm_indexed(d377_ctx* ctx, int64_t handle, const int* base_index, const uint8_t* scalar32, size_t t, size_t n,
+                                 uint8_t* enc32_out, uint64_t* xyzt_out) {
+  if (t < 1 || t > (size_t)FX_MAX)
+    return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_msm_indexed: t must be 1 .. 64 terms per sum (D377_FIXED_BASES_MAX)");
+  if (n && !base_index) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_msm_indexed: base_index is null");
+  if (n && !scalar32) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_msm_indexed: scalar32 is null");
+  if (n && !enc32_out) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_msm_indexed: enc32_out is null");
+  if (!ctx) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_msm_indexed: ctx is null");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  const FixedBases* fb = find(ctx, handle);
+  if (!fb) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_msm_indexed: handle is not a live registration of this context");
+  if (n > SIZE_MAX / 32 / t) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_msm_indexed: n x t overflows");
+  // every index, before any copy or launch: no kernel sees one it could read out of bounds with
+  const size_t terms = n * t;
+  const int m = (int)fb->m;
+  for (size_t p = 0; p < terms; ++p) {
+    const int b = base_index[p];
+    if (b < -1 || b >= m) {
+      snprintf(d377_g_err, sizeof d377_g_err,
+               "d377_batch_fixed_msm_indexed: base_index[%zu] = %d (sum %zu, term %zu) is neither -1 nor a base 0 .. %d of this registration",
+               p, b, p / t, p % t, m - 1);
+      return D377_ERR_ARG;
+    }
   }
-  for (auto& w : workers) w.join();
-  for (size_t k = 0; k < nd; ++k)
-    if (rcs[k] != D377_OK) return fail(rcs[k], "%s", errs[k].c_str());
-  return D377_OK;
+  return fixed_msm_sliced(ctx, *fb, base_index, t, scalar32, n, enc32_out, xyzt_out);
 }
 
 }  // extern "C"

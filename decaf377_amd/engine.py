@@ -641,6 +641,45 @@ class FixedBases:
                 xyzt = torch.from_numpy(xyzt.view(np.int64)).to(tdev)
         return (enc, xyzt) if elements else enc
 
+    def msm_indexed(self, base_index, scalar32, elements=False):
+        """n sums of t terms that name their bases (d377_batch_fixed_msm_indexed):
+
+            out[i] = sum over j < t of scalars[i t + j] * B_{base_index[i, j]}
+
+        base_index: [n, t] int32 (int64 is accepted and range-checked), each 0 .. m-1 or -1 for an absent term -- which
+        costs as much as a present one, so t should be the longest sum's length.  scalar32: [n * t, 32] or [n, t, 32] u8,
+        term-major (any 32 bytes, reduced mod r).  -> enc [n, 32] u8, or (enc, xyzt [n, 16]) with elements=True.  A torch
+        tensor is STAGED through host memory, as in msm, and the results come back on the scalars' device (the indices'
+        if the scalars are no tensor).  An index outside -1 .. m-1 raises NativeError and nothing is computed."""
+        h = self._live()
+        tdev = scalar32.device if _is_torch(scalar32) else (base_index.device if _is_torch(base_index) else None)
+        idx = np.asarray(base_index.detach().cpu().numpy() if _is_torch(base_index) else base_index)
+        if idx.ndim != 2 or idx.dtype.kind not in "iu":
+            raise ValueError("FixedBases.msm_indexed: base_index must be an [n, t] integer array")
+        n, t = idx.shape
+        if idx.dtype != np.int32:
+            if idx.size and (int(idx.min()) < -(1 << 31) or int(idx.max()) >= (1 << 31)):
+                raise ValueError("FixedBases.msm_indexed: base_index does not fit 32 bits")
+            idx = idx.astype(np.int32)
+        idx = np.ascontiguousarray(idx)
+        sc = np.ascontiguousarray(scalar32.detach().cpu().numpy() if _is_torch(scalar32) else scalar32)
+        if sc.ndim == 3:
+            if sc.shape[:2] != (n, t):
+                raise ValueError("FixedBases.msm_indexed: scalars [n, t, 32] must match base_index [n, t]")
+            sc = sc.reshape(n * t, 32)
+        _check(sc, ENC, n * t, "FixedBases.msm_indexed scalars")
+        enc = np.empty((n, 32), np.uint8)
+        xyzt = np.empty((n, 16), np.uint64) if elements else None
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _native.check(self._lib.d377_batch_fixed_msm_indexed(self.ctx._h, h, p(idx), p(sc), ctypes.c_size_t(t), ctypes.c_size_t(n),
+                                                             p(enc), p(xyzt) if elements else None))
+        if tdev is not None:
+            import torch
+            enc = torch.from_numpy(enc).to(tdev)
+            if elements:
+                xyzt = torch.from_numpy(xyzt.view(np.int64)).to(tdev)
+        return (enc, xyzt) if elements else enc
+
     def vartime_multiscalar_mul(self, scalars):
         """The sums' Encodings for an Fr batch (or [n * m, 32] array) of n x m scalars, term-major within a sum."""
         return Encoding(self.msm(scalars.data if isinstance(scalars, _Bytes32) else scalars), self.ctx)

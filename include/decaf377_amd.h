@@ -321,6 +321,20 @@ int d377_batch_msm_small_encoded(d377_ctx* ctx, const uint8_t* enc32, const uint
  * included.  m = 1 is a fixed-base multiplication by B_0.  A multi-GPU context slices the SUMS over its devices.
  * Host pointers only: a device-pointer form is not offered (a Python torch tensor is staged through host memory).
  *
+ * d377_batch_fixed_msm_indexed computes n sums of t terms each, 1 <= t <= D377_FIXED_BASES_MAX, whose terms name their
+ * bases: enc32_out[i] = the canonical Encoding of
+ *     sum over j < t of  scalar[i t + j] * B_{base_index[i t + j]}
+ * (base_index n x t ints and scalar32 n x t 32-byte strings, both term-major within a sum; xyzt_out as above).  An index
+ * is a base's position in the registration, 0 .. m-1; the same index may appear several times in one sum, and the terms
+ * add.  -1 means "this term is absent": it contributes nothing and its scalar bytes are ignored, which is how sums with
+ * fewer than t terms are written -- but an absent term COSTS AS MUCH AS A PRESENT ONE (it walks the identity entries of a
+ * comb), so t should be the longest sum's length, not m.  A sum whose terms are all absent is the identity (the all-zero
+ * Encoding).  Any other index (< -1 or >= m) is D377_ERR_ARG: the whole n x t array is checked on the host before any
+ * copy or launch, the message names base_index and the first offending position, and no output is written.  Arguments
+ * are checked in this order: t, null base_index / scalar32 / enc32_out (n > 0), ctx, the handle, the indices; n == 0 with
+ * good arguments is D377_OK.  With 64 registered bases a two-term sum is 2 W mixed additions where the dense call walks
+ * 64 W and uploads 64 scalars.  Host pointers only, sliced over the devices of a multi-GPU context by SUMS, as above.
+ *
  * Handles: a handle is a positive integer that names one registration within its context (never reused by that
  * context); every call takes the context and the handle, and a handle that was destroyed, or never created there, is
  * refused with D377_ERR_ARG.  Threads and lifetime: calls on one handle, or on several handles of one context, may come
@@ -333,6 +347,8 @@ int d377_fixed_bases_info(d377_ctx* ctx, int64_t handle, uint64_t* m, int* comb_
 int d377_fixed_bases_destroy(d377_ctx* ctx, int64_t handle);
 int d377_batch_fixed_msm(d377_ctx* ctx, int64_t handle, const uint8_t* scalar32, size_t n, uint8_t* enc32_out,
                          uint64_t* xyzt_out);
+int d377_batch_fixed_msm_indexed(d377_ctx* ctx, int64_t handle, const int* base_index, const uint8_t* scalar32, size_t t,
+                                 size_t n, uint8_t* enc32_out, uint64_t* xyzt_out);
 
 /* Fq field operations on in-memory elements (4 Montgomery u64 limbs, R = 2^256, fully reduced), the
  * unit everything above is built from             src/fields/fq/u64/wrapper.rs:99-132, fq/ops.rs

@@ -138,6 +138,22 @@ class FixedBases {
     if (rc != D377_OK) throw DeviceError(rc);
     return enc;
   }
+  /// n sums of t terms that name their bases: sum i = sum over j < t of scalars[i t + j] * B_{base_index[i t + j]} (both
+  /// term-major, n x t each).  An index is 0 .. size() - 1, or -1 for an absent term (which costs as much as a present
+  /// one); anything else makes the library refuse the call (DeviceError, nothing computed).
+  std::vector<Encoding> msm_indexed(const std::vector<int>& base_index, const std::vector<Fr>& scalars, size_t t,
+                                    std::vector<Element>* elements = nullptr) {
+    if (!h_) throw std::logic_error("decaf377_amd: FixedBases used after it was destroyed or its Engine was");
+    if (t == 0 || scalars.size() % t || base_index.size() != scalars.size())
+      throw std::invalid_argument("length mismatch: base_index and scalars must be n x t");
+    std::vector<Encoding> enc(scalars.size() / t);
+    if (elements) elements->assign(enc.size(), Element{});
+    const int rc = d377_batch_fixed_msm_indexed(ctx(), h_, base_index.data(), reinterpret_cast<const uint8_t*>(scalars.data()), t,
+                                                enc.size(), reinterpret_cast<uint8_t*>(enc.data()),
+                                                elements ? reinterpret_cast<uint64_t*>(elements->data()) : nullptr);
+    if (rc != D377_OK) throw DeviceError(rc);
+    return enc;
+  }
   /// table bytes per device
   uint64_t table_bytes() const {
     uint64_t b = 0;

@@ -160,6 +160,20 @@ impl<'a> FixedBases<'a> {
         })?;
         Ok((enc, out.chunks_exact(16).map(element_from_xyzt).collect()))
     }
+    /// n sums of `t` terms that name their bases: sum i = sum over j < t of scalars[i t + j] * B_{base_index[i t + j]}
+    /// (both term-major, n x t each).  An index is 0..m, or -1 for an absent term (which costs as much as a present
+    /// one); any other value is refused by the library before anything is computed.
+    pub fn msm_indexed(&self, base_index: &[i32], scalars: &[Fr], t: usize) -> Result<(Vec<Encoding>, Vec<Element>), GpuError> {
+        assert!(t > 0 && scalars.len() % t == 0 && base_index.len() == scalars.len());
+        let n = scalars.len() / t;
+        let bytes = pack32(scalars, |k| k.to_bytes());
+        let mut enc = vec![Encoding([0u8; 32]); n];
+        let mut out = vec![0u64; 16 * n];
+        check(unsafe {
+            ffi::d377_batch_fixed_msm_indexed(self.ctx.0, self.handle, base_index.as_ptr(), bytes.as_ptr(), t, n, enc.as_mut_ptr() as *mut u8, out.as_mut_ptr())
+        })?;
+        Ok((enc, out.chunks_exact(16).map(element_from_xyzt).collect()))
+    }
 }
 impl Drop for FixedBases<'_> {
     fn drop(&mut self) {

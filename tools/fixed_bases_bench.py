@@ -12,7 +12,17 @@ the PCIe copies of scalars and encodings (32 bytes per term in, 32 per sum out; 
 128-byte Element records per term).  Kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of
 `--only` cases (profiles/README.md).
 
-usage: tools/fixed_bases_bench.py [--quick] [--only m,bits,n[;...]] [--reps 5] [--warmup 2] [--out FILE]"""
+`--indexed` runs the other leg instead, d377_batch_fixed_msm_indexed against d377_batch_fixed_msm (profiles/
+fixed_bases_indexed_bench.json), same conventions:
+
+  what indexing buys    m = 64 bases x comb_bits in {12, 16} x t in {1, 2, 4, 8} terms x n in {2^12, 2^20}: t distinct random
+                        bases per sum, against the dense call on the same sums (zero scalars elsewhere); m / t is the ratio by
+                        addition count
+  what indexing costs   m = t = 8, index row 0 .. 7, 16 bits, 2^20 sums, against the dense call on the same scalars: the same
+                        additions plus the index traffic
+  with --indexed, --only takes cases m,bits,t,n
+
+usage: tools/fixed_bases_bench.py [--indexed] [--quick] [--only m,bits,n[;...]] [--reps 5] [--warmup 2] [--out FILE]"""
 import argparse
 import ctypes
 import json
@@ -38,8 +48,49 @@ def timed(fn, warmup, reps):
     return {"median_ms": round(float(np.median(ts)), 3), "min_ms": round(min(ts), 3), "max_ms": round(max(ts), 3), "reps": reps}
 
 
+def indexed_leg(a, d, ctx, orc, rng, torch):
+    """d377_batch_fixed_msm_indexed against d377_batch_fixed_msm on the same sums."""
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    cases = [(64, bits, t, n) for bits in (12, 16) for n in (1 << 12, 1 << 20) for t in (1, 2, 4, 8)] + [(8, 16, 8, 1 << 20)]
+    if a.only:
+        cases = [tuple(int(x) for x in c.split(",")) for c in a.only.split(";")]
+    pts = np.concatenate([orc.generator_xyzt().reshape(1, 16),
+                          orc.elligator_map_xyzt(rng.integers(0, 256, (63, 32), dtype=np.uint8))]).astype(np.uint64)
+    rec = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "warmup": a.warmup, "path": "host (numpy)", "cases": []}
+    fb, key = None, None
+    for m, bits, t, n in cases:
+        if key != (m, bits):
+            if fb is not None:
+                fb.close()
+            fb, key = ctx.fixed_bases(pts[:m], comb_bits=bits), (m, bits)
+        lib, c, h = fb._lib, ctx._h, fb._h
+        if t == m:                                                # what indexing costs: every base, in registration order
+            idx = np.ascontiguousarray(np.tile(np.arange(m, dtype=np.int32), (n, 1)))
+        else:                                                     # what it buys: t distinct bases per sum
+            idx = np.ascontiguousarray(np.argsort(rng.random((n, m)), axis=1)[:, :t].astype(np.int32))
+        k = rng.integers(0, 256, (n, t, 32), dtype=np.uint8)
+        dense = np.zeros((n, m, 32), np.uint8)
+        dense[np.arange(n)[:, None], idx] = k
+        enc_d, enc_i = np.empty((n, 32), np.uint8), np.empty((n, 32), np.uint8)
+        rd = timed(lambda: d._native.check(lib.d377_batch_fixed_msm(c, h, p(dense), ctypes.c_size_t(n), p(enc_d), None)), a.warmup, a.reps)
+        ri = timed(lambda: d._native.check(lib.d377_batch_fixed_msm_indexed(c, h, p(idx), p(k), ctypes.c_size_t(t), ctypes.c_size_t(n),
+                                                                            p(enc_i), None)), a.warmup, a.reps)
+        assert (enc_d == enc_i).all()
+        r = {"m": m, "bits": bits, "t": t, "n": n, "dense": rd, "indexed": ri,
+             "dense_over_indexed": round(rd["median_ms"] / ri["median_ms"], 2), "by_addition_count": round(m / t, 2),
+             "indexed_median_inside_dense_min_max": rd["min_ms"] <= ri["median_ms"] <= rd["max_ms"],
+             "host_bytes_in_dense": n * m * 32, "host_bytes_in_indexed": n * t * 36}
+        rec["cases"].append(r)
+        print(json.dumps(r), flush=True)
+        del dense
+    if fb is not None:
+        fb.close()
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--indexed", action="store_true", help="d377_batch_fixed_msm_indexed against the dense call (cases m,bits,t,n)")
     ap.add_argument("--quick", action="store_true", help="n in {2^12, 2^20} only")
     ap.add_argument("--only", default="", help="cases m,bits,n separated by ';' (kernel-trace runs)")
     ap.add_argument("--reps", type=int, default=5)
@@ -53,6 +104,14 @@ def main():
     orc = Oracle(build=False)
     ctx = d.Context([0], comb_bits=18)
     rng = np.random.default_rng(377)
+    if a.indexed:
+        rec = indexed_leg(a, d, ctx, orc, rng, torch)
+        ctx.close()
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(json.dumps(rec, indent=1) + "\n")
+        print("FIXED_BASES_BENCH_OK")
+        return
     gen = orc.generator_xyzt().reshape(1, 16)
     pts = np.concatenate([gen, orc.elligator_map_xyzt(rng.integers(0, 256, (7, 32), dtype=np.uint8))]).astype(np.uint64)
     sizes = [1 << 12, 1 << 20] + ([] if a.quick else [1 << 22])
