@@ -42,7 +42,8 @@ D377_HD uint32_t s_hash(const fe& x) {         // lookups: the key must be one o
   return s_hash_raw(x);
 }
 
-D377_HD fe gt_load(const SqrtTables& T, int table, uint32_t idx) {
+template <class F = fe>
+D377_HD F gt_load(const SqrtTables& T, int table, uint32_t idx) {
   const uint32_t* p = T.gtab + ((size_t)table * 256 + idx) * GT_STRIDE;
   fe r;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -55,14 +56,15 @@ D377_HD fe gt_load(const SqrtTables& T, int table, uint32_t idx) {
   for (int i = 0; i < NL; ++i) r.l[i] = p[i];
 #endif
   fe_assume_carried(r, 1.1);      // the init kernels store strict products: value < 1.02q
-  return r;
+  return fe_as<F>(r);
 }
 
 // ---- fixed exponentiations --------------------------------------------------------------
 // Two squarings per trip: the hand-written squarer's outputs may not overlap its inputs, so a one-squaring loop copies
 // the nine limbs back every trip (18 v_mov per 168 instructions); with two the second squaring lands in the first
 // one's input registers and the copies disappear.
-D377_HD fe fe_sqr_n(fe x, int n) {
+template <class F>
+D377_HD F fe_sqr_n(F x, int n) {
 #pragma unroll 1
   for (int i = 0; i + 1 < n; i += 2) x = fe_sqr(fe_sqr(x));
   if (n & 1) x = fe_sqr(x);
@@ -118,23 +120,35 @@ struct RegPowTab {                      // plain registers / stack (host simulat
     return f;
   }
 };
+struct RegPowTabS {                     // the same for a chain on signed limbs (host simulation)
+  fes t[8];
+  D377_HD void put(int j, const fes& v) { t[j] = v; }
+  D377_HD fes get_signed(int j) const { return t[j & 7]; }
+};
+// entry j of a power table in the field type F of the chain: get(j) for fe, get_signed(j) for fes
+template <class F, class PT>
+D377_HD F pt_get(const PT& pt, int j) {
+  if constexpr (std::is_same<F, fe>::value) return pt.get(j);
+  else return pt.get_signed(j);
+}
 
-template <class PT>
-D377_HD fe fe_pow_m12(const fe& x, PT& pt) {
-  fe x2 = fe_sqr(x);
-  fe cur = x;
+// F: the field type the chain runs on (fes: k_scalar_mul_var's decompression)
+template <class F = fe, class PT>
+D377_HD F fe_pow_m12(const F& x, PT& pt) {
+  F x2 = fe_sqr(x);
+  F cur = x;
   pt.put(0, cur);
 #pragma unroll 1
   for (int j = 1; j < POW_TAB; ++j) {
     cur = fe_mul(cur, x2);
     pt.put(j, cur);
   }
-  fe acc = pt.get((int)(D377_POW_CHAIN[0] & 15u) >> 1);
+  F acc = pt_get<F>(pt, (int)(D377_POW_CHAIN[0] & 15u) >> 1);
 #pragma unroll 1
   for (int i = 1; i < D377_POW_LEN; ++i) {
     const uint32_t e = D377_POW_CHAIN[i];
     acc = fe_sqr_n(acc, (int)(e >> 4));
-    acc = fe_mul(acc, pt.get((int)(e & 15u) >> 1));
+    acc = fe_mul(acc, pt_get<F>(pt, (int)(e & 15u) >> 1));
   }
   return fe_sqr_n(acc, D377_POW_TRAIL);
 }
@@ -166,7 +180,11 @@ D377_HD bool fe_strict_is_zero(const fe& a) {
 // The table phase and everything after it (invsqrt.rs:97-166), from v = z^((m-1)/2) and uv = z^((m+1)/2): shared by
 // fe_sqrt_ratio_zeta below and by the callers that raise z to those powers elsewhere (the one-wave-per-element kernels:
 // row_ops.hpp runs the 300 products of the power chains in the lane-spread form).
-D377_HD bool fe_sqrt_tail(const SqrtTables& T, const fe& v, const fe& uv, bool den_zero, bool num_zero, fe* res, bool min_curve_root);
+// F: the field type of the chain.  fes (k_scalar_mul_var only) runs the power chain, the squaring runs and the table products
+// on signed limbs; a value that leaves the chain -- an s_lookup key, the root -- goes back to fe first (fe_unsigned, then
+// the same strict products as on fe: the keys stay one of x, x + q).  The zero tests read the fe operands either way.
+template <class F>
+D377_HD bool fe_sqrt_tail(const SqrtTables& T, const F& v, const F& uv, bool den_zero, bool num_zero, fe* res, bool min_curve_root);
 
 // A "power table" that holds the two powers themselves: the four-elements-per-wave kernels (d377.hip) raise z to them on
 // the rows of the wave and pass the results where the other callers pass the table of the exponentiation.
@@ -178,61 +196,62 @@ struct GivenPowers {
 template <class PT> struct pt_has_powers { static constexpr bool value = false; };
 template <> struct pt_has_powers<GivenPowers> { static constexpr bool value = true; };
 
-template <bool NUM_IS_ONE, class PT>
+template <bool NUM_IS_ONE, class F = fe, class PT>
 D377_HD bool fe_sqrt_ratio_zeta(const SqrtTables& T, PT& pt, const fe& num, const fe& den, fe* res,
                                 bool min_curve_root = false, const fe* inv_den = nullptr, bool use_inv = true) {
   const bool den_zero = fe_strict_is_zero(den);
   bool num_zero = false;
   if (!NUM_IS_ONE) num_zero = fe_strict_is_zero(num);
 
-  fe v, uv;
+  F v, uv;
   // use_inv: a launch-uniform switch for callers that always hold a (possibly meaningless) inverse: a pointer that is
   // null on one path and the address of a local on the other would force that local into scratch memory
   if constexpr (pt_has_powers<PT>::value) {
-    v = pt.v;
-    uv = pt.uv;
+    v = fe_as<F>(pt.v);
+    uv = fe_as<F>(pt.uv);
   } else if (inv_den != nullptr && use_inv) {
-    const fe z = NUM_IS_ONE ? *inv_den : fe_mul(num, *inv_den);
-    v = fe_pow_m12(z, pt);
+    const F z = fe_as<F>(NUM_IS_ONE ? *inv_den : fe_mul(num, *inv_den));
+    v = fe_pow_m12<F>(z, pt);
     uv = fe_mul(v, z);
   } else {
     fe s = fe_pow_2_47_m1(den);                       // invsqrt.rs:88-89
     fe t_ = fe_mul(fe_sqr(s), den);                   // :90
-    fe w = NUM_IS_ONE ? fe_mul(fe_pow_m12(t_, pt), s)     // :91
-                      : fe_mul(fe_pow_m12(fe_mul(num, t_), pt), s);
-    v = fe_mul(w, den);                               // :93
-    uv = NUM_IS_ONE ? w : fe_mul(w, num);             // :94
+    F w = NUM_IS_ONE ? fe_mul(fe_pow_m12<F>(fe_as<F>(t_), pt), fe_as<F>(s))     // :91
+                     : fe_mul(fe_pow_m12<F>(fe_as<F>(fe_mul(num, t_)), pt), fe_as<F>(s));
+    v = fe_mul(w, fe_as<F>(den));                     // :93
+    uv = NUM_IS_ONE ? w : fe_mul(w, fe_as<F>(num));   // :94
   }
   return fe_sqrt_tail(T, v, uv, den_zero, num_zero, res, min_curve_root);
 }
-D377_HD bool fe_sqrt_tail(const SqrtTables& T, const fe& v, const fe& uv, bool den_zero, bool num_zero, fe* res, bool min_curve_root) {
-  fe x5 = fe_mul(uv, v);                            // :97
-  fe x4 = fe_sqr_n(x5, 8);                          // :101-107
-  fe x3 = fe_sqr_n(x4, 8);
-  fe x2 = fe_sqr_n(x3, 8);
-  fe x1 = fe_sqr_n(x2, 8);
-  fe x0 = fe_sqr_strict(fe_sqr_strict(fe_sqr_n(x1, 5)));   // :110  (x1^(2^7))
+template <class F>
+D377_HD bool fe_sqrt_tail(const SqrtTables& T, const F& v, const F& uv, bool den_zero, bool num_zero, fe* res, bool min_curve_root) {
+  F x5 = fe_mul(uv, v);                             // :97
+  F x4 = fe_sqr_n(x5, 8);                           // :101-107
+  F x3 = fe_sqr_n(x4, 8);
+  F x2 = fe_sqr_n(x3, 8);
+  F x1 = fe_sqr_n(x2, 8);
+  fe x0 = fe_sqr_strict(fe_sqr_strict(fe_unsigned(fe_sqr_n(x1, 5))));   // :110  (x1^(2^7))
 
   const uint64_t q0p = T.s_lookup[s_hash(x0)];      // :113
   uint64_t t = q0p;
-  fe a1 = fe_mul_strict(x1, gt_load(T, 4, (uint32_t)(t & 0xFF)));                // :117-119
+  fe a1 = fe_mul_strict(fe_unsigned(x1), gt_load(T, 4, (uint32_t)(t & 0xFF)));   // :117-119
   t += (uint64_t)T.s_lookup[s_hash(a1)] << 7;
-  fe a2 = fe_mul_strict(fe_mul(x2, gt_load(T, 3, (uint32_t)(t & 0xFF))),
+  fe a2 = fe_mul_strict(fe_unsigned(fe_mul(x2, gt_load<F>(T, 3, (uint32_t)(t & 0xFF)))),
                         gt_load(T, 4, (uint32_t)((t >> 8) & 0xFF)));             // :122-126
   t += (uint64_t)T.s_lookup[s_hash(a2)] << 15;
-  fe a3 = fe_mul_strict(fe_mul(fe_mul(x3, gt_load(T, 2, (uint32_t)(t & 0xFF))),
-                               gt_load(T, 3, (uint32_t)((t >> 8) & 0xFF))),
+  fe a3 = fe_mul_strict(fe_unsigned(fe_mul(fe_mul(x3, gt_load<F>(T, 2, (uint32_t)(t & 0xFF))),
+                                           gt_load<F>(T, 3, (uint32_t)((t >> 8) & 0xFF)))),
                         gt_load(T, 4, (uint32_t)((t >> 16) & 0xFF)));            // :129-134
   t += (uint64_t)T.s_lookup[s_hash(a3)] << 23;
-  fe a4 = fe_mul_strict(fe_mul(fe_mul(fe_mul(x4, gt_load(T, 1, (uint32_t)(t & 0xFF))),
-                                      gt_load(T, 2, (uint32_t)((t >> 8) & 0xFF))),
-                               gt_load(T, 3, (uint32_t)((t >> 16) & 0xFF))),
+  fe a4 = fe_mul_strict(fe_unsigned(fe_mul(fe_mul(fe_mul(x4, gt_load<F>(T, 1, (uint32_t)(t & 0xFF))),
+                                                  gt_load<F>(T, 2, (uint32_t)((t >> 8) & 0xFF))),
+                                           gt_load<F>(T, 3, (uint32_t)((t >> 16) & 0xFF)))),
                         gt_load(T, 4, (uint32_t)((t >> 24) & 0xFF)));            // :137-143
   t += (uint64_t)T.s_lookup[s_hash(a4)] << 31;
-  fe a5 = fe_mul_strict(fe_mul(fe_mul(fe_mul(fe_mul(x5, gt_load(T, 0, (uint32_t)(t & 0xFF))),
-                                             gt_load(T, 1, (uint32_t)((t >> 8) & 0xFF))),
-                                      gt_load(T, 2, (uint32_t)((t >> 16) & 0xFF))),
-                               gt_load(T, 3, (uint32_t)((t >> 24) & 0xFF))),
+  fe a5 = fe_mul_strict(fe_unsigned(fe_mul(fe_mul(fe_mul(fe_mul(x5, gt_load<F>(T, 0, (uint32_t)(t & 0xFF))),
+                                                         gt_load<F>(T, 1, (uint32_t)((t >> 8) & 0xFF))),
+                                                  gt_load<F>(T, 2, (uint32_t)((t >> 16) & 0xFF))),
+                                           gt_load<F>(T, 3, (uint32_t)((t >> 24) & 0xFF)))),
                         gt_load(T, 4, (uint32_t)((t >> 32) & 0xFF)));            // :146-153
   t += (uint64_t)T.s_lookup[s_hash(a5)] << 39;
 
@@ -241,14 +260,15 @@ D377_HD bool fe_sqrt_tail(const SqrtTables& T, const fe& v, const fe& uv, bool d
   const bool flip = min_curve_root && (((D377_TS_U * e2) >> 46) & 1ull) != 0;
   t = (t + 1) >> 1;                                                              // :155
   const bool nonsq = (q0p & 1) != 0;
-  fe r = fe_select(nonsq, fe_mul(uv, fe_const(FE_NONSQUARE)), uv);               // :156-157
-  r = fe_mul(r, gt_load(T, 0, (uint32_t)(t & 0xFF)));
-  r = fe_mul(r, gt_load(T, 1, (uint32_t)((t >> 8) & 0xFF)));
-  r = fe_mul(r, gt_load(T, 2, (uint32_t)((t >> 16) & 0xFF)));
-  r = fe_mul(r, gt_load(T, 3, (uint32_t)((t >> 24) & 0xFF)));
-  r = fe_mul(r, gt_load(T, 4, (uint32_t)((t >> 32) & 0xFF)));
-  r = fe_mul(r, gt_load(T, 5, (uint32_t)((t >> 40) & 0xFF)));                    // :158-163
+  F rf = fe_select(nonsq, fe_mul(uv, fe_as<F>(fe_const(FE_NONSQUARE))), uv);     // :156-157
+  rf = fe_mul(rf, gt_load<F>(T, 0, (uint32_t)(t & 0xFF)));
+  rf = fe_mul(rf, gt_load<F>(T, 1, (uint32_t)((t >> 8) & 0xFF)));
+  rf = fe_mul(rf, gt_load<F>(T, 2, (uint32_t)((t >> 16) & 0xFF)));
+  rf = fe_mul(rf, gt_load<F>(T, 3, (uint32_t)((t >> 24) & 0xFF)));
+  rf = fe_mul(rf, gt_load<F>(T, 4, (uint32_t)((t >> 32) & 0xFF)));
+  rf = fe_mul(rf, gt_load<F>(T, 5, (uint32_t)((t >> 40) & 0xFF)));               // :158-163
 
+  fe r = fe_unsigned(rf);                           // the root leaves the chain (fes: carried, below 2q + a product's bound)
   if (min_curve_root) r = fe_select(flip, fe_neg(r), r);
   bool was_square = !nonsq;
   // early-outs of invsqrt.rs:81-86, applied as selects so the wave stays converged
@@ -632,10 +652,11 @@ D377_HD uint32_t ge_decompress_with(const SqrtTables& T, const uint32_t w[8], ge
   D377_INVARIANT(T, *out, bad == 0);                      // encoding.rs:75-78 / element.rs:104-110
   return bad;
 }
-template <class PT>
+// F: the field type of the square root's chain (fe_sqrt_ratio_zeta)
+template <class F = fe, class PT>
 D377_HD uint32_t ge_decompress(const SqrtTables& T, PT& pt, const uint32_t w[8], ge* out, const fe* inv_den = nullptr) {
   return ge_decompress_with(T, w, out, [&](const fe& den, fe* v) {
-    return fe_sqrt_ratio_zeta<true>(T, pt, fe_zero(), den, v, false, inv_den);
+    return fe_sqrt_ratio_zeta<true, F>(T, pt, fe_zero(), den, v, false, inv_den);
   });
 }
 // the same with v = (1/den)^((m-1)/2), uv = (1/den)^((m+1)/2) raised elsewhere (see fe_sqrt_tail)
@@ -953,7 +974,10 @@ D377_HD ge ge_double_latency(const ge& p) { return ge_double_fast(p, true); }
 template <class F>
 D377_HD gec_of<F> ge_to_cached(const ge_of<F>& p) {
   gec_of<F> c;
-  c.ypx = fe_carry(fe_add(p.y, p.x));     // carried, like ymx: a negative digit swaps the two
+  // carried, like ymx: a negative digit swaps the two.  (fes: the lazy sum as it is -- limbs below 2^30 against operands
+  // below 2^30 keep every column inside +-2^63, which the bounds build proves for each product that reads an entry.)
+  if constexpr (std::is_same<F, fes>::value) c.ypx = fe_add(p.y, p.x);
+  else c.ypx = fe_carry(fe_add(p.y, p.x));
   c.ymx = fe_sub(p.y, p.x);               // carried
   c.z2 = fe_dbl(p.z);                     // lazy
   c.kt = fe_mul(fe_as<F>(fe_const(FE_K)), p.t);
@@ -1028,15 +1052,23 @@ D377_HD ge ge_from_cached_affine(const gea& q, bool neg) {
 // want_t: whether the caller uses T of the result (the square-root-free compressor does not).
 // F: the field type of the table and the loop (fes: Tab stores and loads gec_of<fes>); p and the result are fe points
 // (fe -> fes is free; at the end each coordinate goes back to a carried fe, fe_unsigned: no product).
+// Entry 0, the cached identity, is the same record for every lane and element: a table that declares
+// `static constexpr bool shared_identity = true` serves load(0, .) from one constant record of its own (gec_identity)
+// and is never handed a store(0, .); every other table has it stored like entries 1..8.
+template <class F>
+D377_HD gec_of<F> gec_identity() {
+  gec_of<F> id;
+  id.ypx = fe_as<F>(fe_const(FE_ONE)); id.ymx = fe_as<F>(fe_const(FE_ONE)); id.z2 = fe_dbl(fe_as<F>(fe_const(FE_ONE)));
+  id.kt = fe_as<F>(fe_zero());
+  return id;
+}
+template <class Tab, class = void> struct tab_shares_identity { static constexpr bool value = false; };
+template <class Tab> struct tab_shares_identity<Tab, std::void_t<decltype(Tab::shared_identity)>> { static constexpr bool value = Tab::shared_identity; };
+
 template <class F = fe, class Tab>
 D377_HD ge ge_scalar_mul_w4(const ge& p0, const uint32_t digits[8], Tab& tab, bool want_t = true) {
   const ge_of<F> p = ge_as<F>(p0);
-  {
-    gec_of<F> id;
-    id.ypx = fe_as<F>(fe_const(FE_ONE)); id.ymx = fe_as<F>(fe_const(FE_ONE)); id.z2 = fe_dbl(fe_as<F>(fe_const(FE_ONE)));
-    id.kt = fe_as<F>(fe_zero());
-    tab.store(0, id);
-  }
+  if constexpr (!tab_shares_identity<Tab>::value) tab.store(0, gec_identity<F>());
   const gec_of<F> pc = ge_to_cached(p);
   tab.store(1, pc);
   ge_of<F> acc = ge_double_fast(p, true);

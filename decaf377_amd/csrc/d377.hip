@@ -38,17 +38,22 @@ namespace {
 // [entry][thread][4 slots x 12 words]: a wave stores one entry as 12 KiB contiguous, and a lane
 // fetches its 192-byte (three 64-B sectors) record with 16-byte loads.  A negative digit
 // swaps the ypx / ymx slots by address.  F: the field type of the chain that uses it (fes: the signed window loop,
-// same records bit for bit).
+// same records bit for bit).  Entry 0, the cached identity, is one constant record per device (DeviceState::vb_identity,
+// written once by k_init_vb_identity): no lane stores it, load(0, .) takes the shared record by address select, and the
+// lanes' own slots 0 of the scratch stay unused.
 template <class F>
 struct GlobalTab {
+  static constexpr bool shared_identity = true;         // curve.hpp, ge_scalar_mul_w4: entry 0 is never stored
   uint32_t* base;
+  const uint32_t* ident;
   size_t nthreads, tid;
   __device__ __forceinline__ void store(int j, const gec_of<F>& c) {
     uint32_t* p = base + ((size_t)j * nthreads + tid) * VB_ENTRY_WORDS;
     slot_store(p, c.ypx); slot_store(p + SLOT, c.ymx); slot_store(p + 2 * SLOT, c.z2); slot_store(p + 3 * SLOT, c.kt);
   }
   __device__ __forceinline__ gec_of<F> load(int j, bool swap) const {
-    const uint32_t* p = base + ((size_t)j * nthreads + tid) * VB_ENTRY_WORDS;
+    const uint32_t* own = base + ((size_t)j * nthreads + tid) * VB_ENTRY_WORDS;
+    const uint32_t* p = j == 0 ? ident : own;
     gec_of<F> c;
     c.ypx = slot_load_as<F>(p + (swap ? SLOT : 0));
     c.ymx = slot_load_as<F>(p + (swap ? 0 : SLOT));
@@ -91,6 +96,13 @@ __global__ void __launch_bounds__(BLOCK) k_init_gtab(uint32_t* gtab) {
 #pragma unroll
   for (int i = 0; i < NL; ++i) p[i] = v.l[i];
   p[9] = 0; p[10] = 0; p[11] = 0;
+}
+
+// entry 0 of every variable-base window table (GlobalTab): the cached identity, one VB_ENTRY_WORDS record per device
+__global__ void k_init_vb_identity(uint32_t* rec) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const gec_of<fes> id = gec_identity<fes>();
+  slot_store(rec, id.ypx); slot_store(rec + SLOT, id.ymx); slot_store(rec + 2 * SLOT, id.z2); slot_store(rec + 3 * SLOT, id.kt);
 }
 
 // s_lookup: keys g^-(nu * 2^39) (invsqrt.rs:27-39) in both tight representations -> nu.
@@ -383,11 +395,13 @@ __global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD) k_hash_to_curve(SqrtTab
 // [k]P = [2]([k/2 mod r]P): the window loop runs on k/2 and the encoding is that of the double (no square root)
 __global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD) k_scalar_mul_var(SqrtTables T, const uint8_t* enc32,
                                                           const uint8_t* scalar32, size_t n, uint8_t* out32,
-                                                          uint8_t* status, uint32_t* scratch, DcbScratch dcb) {
+                                                          uint8_t* status, uint32_t* scratch, const uint32_t* vb_identity,
+                                                          DcbScratch dcb) {
   D377_POW_LDS();
   D377_DCB_BEGIN(out32);
   GlobalTab<fes> tab;                                   // the window loop in signed limbs (fqs29.hpp)
   tab.base = scratch;
+  tab.ident = vb_identity;
   tab.nthreads = (size_t)dcb.nslots * BLOCK;            // the window tables exist for this kernel's sets only (vb_scratch)
   tab.tid = io.lane;
   dcb_rounds<1, true, false>(n, io, pt,
@@ -402,7 +416,7 @@ __global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD) k_scalar_mul_var(SqrtTa
       load32(scalar32, i, k);
       const fe inv = fe_from_words(invw[0]);
       ge g;
-      const uint32_t bad = ge_decompress(T, pt, w, &g, &inv);
+      const uint32_t bad = ge_decompress<fes>(T, pt, w, &g, &inv);    // the square root's chain in signed limbs too
       status[i] = (uint8_t)bad;
       fr_reduce_words(k);
       fr_half_words(k);
@@ -892,12 +906,14 @@ __global__ void __launch_bounds__(64) k_hash_to_curve_tiny2(SqrtTables T, const 
 // end.  An Element leaves as whatever projective representative the schedule here produces -- the group element
 // (and so its encoding, and decaf equality) is the reference's; its X:Y:Z:T need not be.
 __global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD) k_scalar_mul_var_el(const uint64_t* xyzt, const uint8_t* scalar32, size_t n,
-                                                                             uint64_t* out, uint32_t* scratch, DcbScratch dcb) {
+                                                                             uint64_t* out, uint32_t* scratch, const uint32_t* vb_identity,
+                                                                             DcbScratch dcb) {
   // chunked like the kernels above (one workgroup per per_lane x 256 elements, a claimed set of window tables)
   const int slot = dcb_claim(dcb);
   if (slot < 0) return;
   GlobalTab<fes> tab;                                   // the window loop in signed limbs (fqs29.hpp)
   tab.base = scratch;
+  tab.ident = vb_identity;
   tab.nthreads = (size_t)dcb.nslots * BLOCK;
   tab.tid = (size_t)slot * BLOCK + threadIdx.x;
   const size_t chunk_elems = (size_t)dcb.per_lane * BLOCK;
@@ -1475,6 +1491,9 @@ int init_device(DeviceState& d) {
   d.vb_blocks = d.cus * WAVES_PER_SIMD;        // exactly the resident blocks: 2 per CU
 
   HIP_TRY(hipMalloc(&d.vb_scratch, (size_t)d.vb_blocks * BLOCK * VB_ENTRIES * VB_ENTRY_WORDS * sizeof(uint32_t)));
+  HIP_TRY(hipMalloc(&d.vb_identity, VB_ENTRY_WORDS * sizeof(uint32_t)));
+  hipLaunchKernelGGL(k_init_vb_identity, dim3(1), dim3(64), 0, d.stream, d.vb_identity);
+  HIP_TRY(hipGetLastError());
   // round records of the batched inversions: DCB_SLOTS x DCB_KMAX 32-byte records per lane of every lane set (480 MiB), and the
   // pool of lane sets the workgroups claim
   for (int k = 0; k < CK_COUNT; ++k) { d.chunk_sets[k] = WAVES_PER_SIMD; d.chunk_k[k] = DCB_K; }
@@ -1510,7 +1529,7 @@ void free_device(DeviceState& d) {
   if (d.copy_stream) (void)hipStreamSynchronize(d.copy_stream);
   (void)d.vb_guard.drain();
   (void)d.msm.guard.drain();
-  (void)hipFree(d.gtab); (void)hipFree(d.s_lookup); (void)hipFree(d.fbase); (void)hipFree(d.fb_bases); (void)hipFree(d.bm_scratch); (void)hipFree(d.vb_scratch); (void)hipFree(d.dcb_scratch); (void)hipFree(d.slot_pool); (void)hipFree(d.pool_health); (void)hipFree(d.inv_fail);
+  (void)hipFree(d.gtab); (void)hipFree(d.s_lookup); (void)hipFree(d.fbase); (void)hipFree(d.fb_bases); (void)hipFree(d.bm_scratch); (void)hipFree(d.vb_scratch); (void)hipFree(d.vb_identity); (void)hipFree(d.dcb_scratch); (void)hipFree(d.slot_pool); (void)hipFree(d.pool_health); (void)hipFree(d.inv_fail);
   if (d.starve_host) (void)hipHostFree(d.starve_host);
   d.starve_host = nullptr;
   if (d.pool_host) (void)hipHostFree(d.pool_host);
@@ -1688,7 +1707,7 @@ int launch(DeviceState& d, hipStream_t s, Op op, int aux, const void* in0, const
       }
       if ((rc = vb.acquire())) return rc;
       hipLaunchKernelGGL(k_scalar_mul_var, dim3(gv), dim3(BLOCK), d.chunk_lds[CK_MUL_VAR], s, T, (const uint8_t*)in0, (const uint8_t*)in1, n,
-                         (uint8_t*)out0, (uint8_t*)out1, d.vb_scratch, dcb);
+                         (uint8_t*)out0, (uint8_t*)out1, d.vb_scratch, (const uint32_t*)d.vb_identity, dcb);
       break;
     case OP_ENCODE:
       if (n <= tiny4_batch_max(d)) {
@@ -1790,7 +1809,7 @@ int launch(DeviceState& d, hipStream_t s, Op op, int aux, const void* in0, const
       dv.prio = nch <= 2 * (size_t)d.cus * WAVES_PER_SIMD ? 1 : 0;
       if ((rc = vb.acquire())) return rc;
       hipLaunchKernelGGL(k_scalar_mul_var_el, dim3((int)nch), dim3(BLOCK), d.chunk_lds[CK_MUL_VAR_EL], s, (const uint64_t*)in0, (const uint8_t*)in1, n,
-                         (uint64_t*)out0, d.vb_scratch, dv);
+                         (uint64_t*)out0, d.vb_scratch, (const uint32_t*)d.vb_identity, dv);
       break;
     }
     case OP_MUL_BASE_EL:

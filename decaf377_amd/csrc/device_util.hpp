@@ -156,6 +156,17 @@ struct LdsPowTab {
     for (int k = 0; k < NL; ++k) r.l[k] = col[(j * NL + k) * BLOCK];
     return r;
   }
+  // the same slots holding signed-limb elements (fqs29.hpp): the limbs' bit patterns, as slot_store(fes) keeps them
+  __device__ __forceinline__ void put(int j, const fes& v) {
+#pragma unroll
+    for (int k = 0; k < NL; ++k) col[(j * NL + k) * BLOCK] = (uint32_t)v.l[k];
+  }
+  __device__ __forceinline__ fes get_signed(int j) const {
+    fes r;
+#pragma unroll
+    for (int k = 0; k < NL; ++k) r.l[k] = (int32_t)col[(j * NL + k) * BLOCK];
+    return r;
+  }
 };
 // ---- 128-byte records through LDS: coalesced --------------------------------------------------------------------------
 // A lane that loads its own 128-byte record issues eight 16-byte loads at a lane stride of 128 bytes: every instruction

@@ -117,6 +117,7 @@ struct DeviceState {
   int fb_bits = FB_BITS;                 // the comb's width: the build's default, or d377_ctx_opts::comb_bits (18 / 21 / 23)
   bool fb_lazy = false;                  // d377_ctx_opts::comb_lazy
   uint32_t* vb_scratch = nullptr;
+  uint32_t* vb_identity = nullptr;        // the window tables' shared entry 0 (d377.hip GlobalTab)
   uint8_t* dcb_scratch = nullptr;        // round records of the batched inversions (curve.hpp: dcb_invert_slot, dcb_finish)
   int* slot_pool = nullptr;              // which of the lane sets of the scratch areas are claimed, and by which ticket (dcb.hpp, DcbScratch)
   uint32_t* pool_health = nullptr;       // ticket counter, workgroups that waited long for a set, workgroups that gave up (dcb.hpp)
