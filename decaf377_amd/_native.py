@@ -42,6 +42,7 @@ EXPORTS = [
     "d377_batch_msm_small", "d377_batch_msm_small_encoded", "d377_batch_msm_small_dev", "d377_batch_msm_small_encoded_dev",
     "d377_fixed_bases_create", "d377_fixed_bases_info", "d377_fixed_bases_destroy", "d377_batch_fixed_msm",
     "d377_batch_fixed_msm_indexed",
+    "d377_batch_msm_long", "d377_batch_msm_long_encoded",
 ]
 
 
@@ -188,8 +189,11 @@ def load():
     lib.d377_batch_msm_small_encoded.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
     lib.d377_batch_msm_small_dev.argtypes = [vp, i32, vp, vp, vp, sz, sz, vp, vp]
     lib.d377_batch_msm_small_encoded_dev.argtypes = [vp, i32, vp, vp, vp, sz, sz, vp, vp, vp]
+    lib.d377_batch_msm_long.argtypes = [vp, vp, vp, sz, sz, vp, vp]
+    lib.d377_batch_msm_long_encoded.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
     for name in ("d377_msm", "d377_msm_encoded", "d377_msm_dev", "d377_msm_encoded_dev", "d377_sum_elements_dev",
-                 "d377_batch_msm_small", "d377_batch_msm_small_encoded", "d377_batch_msm_small_dev", "d377_batch_msm_small_encoded_dev"):
+                 "d377_batch_msm_small", "d377_batch_msm_small_encoded", "d377_batch_msm_small_dev", "d377_batch_msm_small_encoded_dev",
+                 "d377_batch_msm_long", "d377_batch_msm_long_encoded"):
         getattr(lib, name).restype = i32
     lib.d377_fixed_bases_create.argtypes = [vp, vp, sz, i32, ctypes.POINTER(ctypes.c_int64)]
     lib.d377_fixed_bases_info.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_uint64)]

@@ -1,0 +1,427 @@
+// batch_msm_long.hip -- many multiscalar sums of 9 .. 4096 terms each (gfx950): out[i] = sum_{j < m} scalar[i m + j] * point[i m + j].
+//
+// Between d377_msm (ONE sum per call, Pippenger, a floor of a quarter of a millisecond) and d377_batch_msm_small (n sums of at
+// most 8 terms) a caller with a thousand sums of a few hundred terms had to call one n times or compose the other with rounds
+// of additions through host memory.  Here every sum is cut into g = ceil(m / 8) groups of b = ceil(m / g) terms
+// (batch_msm_long_plan.hpp), every group is the Straus chain of the small sums (straus.hpp, unchanged), and the g partial
+// sums of a sum are folded on the device:
+//
+//   k_msm_long_lane   one lane per PARTIAL sum, in chunks with the per-lane table scratch of batch_msm.hip's lane kernel (the
+//                     same area, b <= 8 tables per lane); every chain of a launch runs b slots, the slots of a sum's last
+//                     group that lie past its end are dead and read nothing
+//   k_msm_long_wave   one wave per partial sum in the lane-spread form (row_ops.hpp), tables in LDS: calls of up to four
+//                     partial sums per SIMD (one sum of 4096 terms is 512 of them)
+//   k_msm_long_fold   one lane adds up to BML_FOLD = 16 consecutive partial sums of one sum (the full addition of k_add on
+//                     records, no conversion); repeated until one record per sum is left -- three levels at g = 512
+//
+// The chains write their partial sums as Element records (the double of the chain's result, as xyzt_out of the small sums)
+// and skip the compressor; the last fold level's records go through the chunked compressor with batched inversions
+// (codec_chunked.hip).  Everything below the host copy layer works on device pointers and a stream.
+//
+// A translation unit of its own, like batch_msm.hip: the register tables of the other units' kernels are measured artefacts.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <chrono>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/decaf377_amd.h"
+#include "curve.hpp"
+#include "device_util.hpp"
+#include "dcb.hpp"
+#include "quad_ops.hpp"
+#include "row_ops.hpp"
+#include "straus.hpp"
+#include "host_state.hpp"
+#include "codec_chunked.hpp"
+#include "batch_msm_long_plan.hpp"
+
+using namespace d377;
+
+namespace {
+
+constexpr size_t BML_MAX = D377_BATCH_MSM_LONG_MAX_TERMS;
+static_assert(BML_GROUP_MAX == D377_BATCH_MSM_MAX_TERMS, "a group is one chain of the small sums");
+static_assert(VB_ENTRIES == 9, "straus_sum stores entries 0 .. 8 of every point's table");
+
+// batch_msm.hip's StrausTab, restated (that unit keeps its source): the scratch of one resident lane, tables
+// [point][entry][lane] and digit words [window][lane]
+struct StrausTab {
+  uint32_t* tab;
+  uint32_t* dig;
+  size_t nthreads, tid;
+  __device__ __forceinline__ uint32_t* entry(int p, int j) const { return tab + (((size_t)p * VB_ENTRIES + j) * nthreads + tid) * VB_ENTRY_WORDS; }
+  __device__ __forceinline__ void store(int p, int j, const gec& c) {
+    uint32_t* q = entry(p, j);
+    slot_store(q, c.ypx); slot_store(q + SLOT, c.ymx); slot_store(q + 2 * SLOT, c.z2); slot_store(q + 3 * SLOT, c.kt);
+  }
+  __device__ __forceinline__ gec load(int p, int j, bool swap) const {
+    const uint32_t* q = entry(p, j);
+    gec c;
+    c.ypx = slot_load(q + (swap ? SLOT : 0));
+    c.ymx = slot_load(q + (swap ? 0 : SLOT));
+    c.z2 = slot_load(q + 2 * SLOT);
+    c.kt = slot_load(q + 3 * SLOT);
+    return c;
+  }
+  __device__ __forceinline__ void dig_store(int w, uint32_t v) { dig[(size_t)w * nthreads + tid] = v; }
+  __device__ __forceinline__ uint32_t dig_load(int w) const { return dig[(size_t)w * nthreads + tid]; }
+};
+
+// ---- one lane per partial sum -----------------------------------------------------------------------------------------------
+// np = n g partial sums; partial p = s g + q reads the terms from s m + q b.  status: one byte per TERM, written for live slots only.
+template <bool ENCODED>
+__global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD)
+k_msm_long_lane(SqrtTables T, const void* pts_in, const uint8_t* scalar32, LongPlan plan, size_t np, uint64_t* partials,
+                uint8_t* status, uint32_t* tab, uint32_t* dig, DcbScratch dcb) {
+  __shared__ uint32_t lds_pow_[ENCODED ? POW_TAB * NL * BLOCK : 1];
+  LdsPowTab pt;
+  pt.col = lds_pow_ + (ENCODED ? threadIdx.x : 0);
+  D377_DCB_BEGIN(partials);                                  // (no compressor here: the chunk walk never writes through io.out32)
+  StrausTab st{tab, dig, (size_t)dcb.nslots * BLOCK, io.lane};
+  dcb_rounds<0, false>(np, io, pt,
+    [&](size_t, int) {},
+    [&](size_t i, int, const uint32_t (*)[8], bool) {
+      const size_t s = i / plan.g, q = i % plan.g;
+      const size_t first = s * plan.m + plan.first(q);
+      const int live = (int)plan.count(q);                   // 1 .. b; the slots from `live` on are past the end of the sum
+      const ge r = straus_sum(st, (int)plan.b, [&](int p, uint32_t k[8]) {
+        if (p < live) { load32(scalar32, first + (size_t)p, k); return; }
+#pragma unroll
+        for (int w = 0; w < 8; ++w) k[w] = 0;                 // a dead slot: no scalar read
+      }, [&](int p, ge* g) -> bool {
+        if (p >= live) { *g = ge_identity(); return true; }   // a dead slot: no point read, no status write
+        if (ENCODED) {
+          uint32_t w[8];
+          load32(reinterpret_cast<const uint8_t*>(pts_in), first + (size_t)p, w);
+          const uint32_t bad = ge_decompress(T, pt, w, g);
+          status[first + (size_t)p] = (uint8_t)bad;
+          return bad != 0;
+        }
+        *g = load_ge_mont256(reinterpret_cast<const uint64_t*>(pts_in), first + (size_t)p);
+        D377_INVARIANT(T, *g, !fe_is_zero(g->z));
+        return fe_is_zero(g->z);                              // a record with Z = 0 is no group element: the identity
+      }, DCB_WANT_T);
+      store_ge_mont256(partials, i, ge_double_fast(r, true)); // the chain ran on k / 2: the partial sum is the double
+    });
+  D377_DCB_END();
+}
+
+// ---- one wave per partial sum: batch_msm.hip's k_batch_msm_wave on a group, without the compressor --------------------------
+// The chain's term count is uniform over the workgroup, so the wave form runs the group's live terms only: it has no dead slots.
+using row::RQ_WORDS;
+static_assert(POW_TAB * 64 <= row::RQ_TAB_ENTRIES * RQ_WORDS, "row_sqrt_powers' scratch must fit in one point's LDS table");
+template <bool ENCODED>
+__global__ void __launch_bounds__(64)
+k_msm_long_wave(SqrtTables T, const void* pts_in, const uint8_t* scalar32, LongPlan plan, size_t np, uint64_t* partials,
+                uint8_t* status) {
+  extern __shared__ uint32_t tab[];                                // b tables of RQ_TAB_ENTRIES x RQ_WORDS words (dynamic: 2 304 bytes per term)
+  __shared__ uint32_t xrec[2 * RQ_WORDS];
+  __shared__ uint32_t sdg[BML_GROUP_MAX][8];                       // the points' signed digits (wave-uniform reads in the loop)
+  const int t = threadIdx.x;
+  const row::RowK K = row::row_consts();
+  const row::RowSel S = row::row_sel();
+  const size_t part = blockIdx.x;                                  // grid = np
+  if (part >= np) return;
+  const size_t gq = part % plan.g;
+  const size_t first = (part / plan.g) * plan.m + plan.first(gq);
+  const int m = (int)plan.count(gq);
+#pragma unroll 1
+  for (int base = 0; base < m; base += 4) {
+    const int pj = t & 3;
+    const bool mine = base + pj < m;
+    const size_t e_mine = first + (size_t)(mine ? base + pj : 0);
+    ge g;
+    bool skip = !mine;
+    if (ENCODED) {
+      uint32_t w[8];
+      load32(reinterpret_cast<const uint8_t*>(pts_in), e_mine, w);
+      if (t < 4) row::row_store_from_fe(xrec + 16 * t, ge_decompress_den(w));
+      __syncthreads();
+      const row::RowPowers pw = row::row_sqrt_powers(xrec[t], tab + base * row::RQ_TAB_ENTRIES * RQ_WORDS, t, K);   // (this group's tables: not built yet)
+      __syncthreads();
+      xrec[t] = pw.v; xrec[RQ_WORDS + t] = pw.uv;
+      __syncthreads();
+      const fe pv = row::row_load_to_fe(xrec + 16 * pj), puv = row::row_load_to_fe(xrec + RQ_WORDS + 16 * pj);
+      __syncthreads();
+      const uint32_t bad = ge_decompress_from_powers(T, w, pv, puv, &g);
+      if (t < 4 && mine) status[e_mine] = (uint8_t)bad;
+      skip |= bad != 0;
+    } else {
+      g = load_ge_mont256(reinterpret_cast<const uint64_t*>(pts_in), e_mine);
+      skip |= fe_is_zero(g.z);
+      D377_INVARIANT(T, g, t < 4 && !skip);
+    }
+#pragma unroll 1
+    for (int j = 0; j < 4 && base + j < m; ++j) {
+      uint32_t k[8], dg[8];
+      load32(scalar32, first + (size_t)(base + j), k);
+      fr_reduce_words(k);
+      fr_half_words(k);
+      fr_recode_signed16(k, dg);
+      if (pj == j && t < 16) row::row_store_from_fe(xrec + 16 * (t >> 2), fe_pick(t >> 2, g.x, g.y, g.z, g.t));
+      __syncthreads();
+      const bool dead = __shfl((int)skip, j) != 0;                  // (wave-uniform: lane j's verdict on point base + j)
+      if (t < 8) sdg[base + j][t] = dead ? 0u : dg[t];              // dead: every digit 0
+      row::rq_build_table(dead ? row::rq_identity(S) : xrec[t], tab + (base + j) * row::RQ_TAB_ENTRIES * RQ_WORDS, S, K);
+      __syncthreads();
+    }
+  }
+  uint32_t v = row::rq_identity(S);
+#pragma unroll 1
+  for (int i = 63; i >= 0; --i) {
+    if (i != 63) {
+#pragma unroll 1
+      for (int k = 0; k < 4; ++k) v = row::rq_double_neg(v, S, K);  // four sign-folded doublings keep the sign
+    }
+#pragma unroll 1
+    for (int j = 0; j < m; ++j) {
+      const int d = fr_digit(sdg[j], i);
+      if (d != 0) v = row::rq_add(v, tab + (j * row::RQ_TAB_ENTRIES + (d < 0 ? -d : d)) * RQ_WORDS, S, d < 0, K);
+    }
+  }
+  __syncthreads();
+  xrec[t] = v;
+  __syncthreads();
+  const ge r = row::rq_load_point(xrec);
+  if (t == 0) store_ge_mont256(partials, part, ge_double_fast(r, true));
+}
+
+// ---- the fold: c records per sum -> ceil(c / BML_FOLD) ------------------------------------------------------------------------
+// Lane L = s oc + f adds the records [f BML_FOLD, f BML_FOLD + fold_count) of sum s with k_add's full addition on the records as
+// they lie in memory (curve.hpp, "records used without conversion") and writes record L of the next level.  A lane's records
+// are consecutive: 2 KiB per lane.  Lanes past the end of the level do nothing; a sum's last lane may add fewer records.
+__global__ void __launch_bounds__(BLOCK) k_msm_long_fold(const uint64_t* in, size_t c, size_t nsums, uint64_t* out) {
+  const size_t oc = fold_out(c), total = nsums * oc;
+  for (size_t L = (size_t)blockIdx.x * BLOCK + threadIdx.x; L < total; L += (size_t)gridDim.x * BLOCK) {
+    const size_t s = L / oc, f = L % oc;
+    const size_t lo = s * c + f * BML_FOLD;
+    const int cnt = (int)fold_count(c, f);
+    uint32_t acc[32];
+    load_record128(in, lo, acc);
+#pragma unroll 1
+    for (int j = 1; j < cnt; ++j) {
+      uint32_t q[32], r[32];
+      load_record128(in, lo + (size_t)j, q);
+      ge_add_raw_words(acc, q, false, r);
+#pragma unroll
+      for (int w = 0; w < 32; ++w) acc[w] = r[w];
+    }
+    store_record128(out, L, acc);
+  }
+}
+
+// ------------------------------------------------------------------------------ host side ---
+int fail_size(int code, const char* fmt, size_t a) {
+  char msg[256];
+  snprintf(msg, sizeof msg, fmt, a);
+  return fail(code, "%s", msg);
+}
+
+// records the area must hold for n sums of g partial sums: the partial sums, then the two halves the fold levels alternate between
+size_t partial_records(size_t n, size_t g) { return n * g + 2 * n * fold_out(g); }
+
+// the per-device partials area: grown on demand, never shrunk.  The caller holds ctx->mu and the lane-set guard's scope.
+int ensure_partials(DeviceState& d, size_t bytes) {
+  if (bytes <= d.bml_cap) return D377_OK;
+  int rc;
+  if ((rc = d.vb_guard.drain())) return rc;                  // (every user of the area queues behind the guard)
+  if (d.bml_partials) HIP_TRY(hipFree(d.bml_partials));
+  d.bml_partials = nullptr; d.bml_cap = 0;
+  const size_t want = bytes + bytes / 4 + 4096;
+  if (hipMalloc(&d.bml_partials, want) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail_size(D377_ERR_HIP, "batch_msm_long: hipMalloc of the partial sums' area failed (%zu bytes: 128 bytes per group of up to 8 terms)", want);
+  }
+  d.bml_cap = want;
+  return D377_OK;
+}
+
+// everything on device pointers, enqueued on `s`; the caller holds ctx->mu.  m > 8.
+int batch_msm_long_launch(DeviceState& d, hipStream_t s, bool encoded, const void* pts_in, const uint8_t* scalars, size_t m, size_t n,
+                          uint8_t* out32, uint64_t* xyzt_out, uint8_t* status) {
+  if (n == 0) return D377_OK;
+  const SqrtTables T = d.tables();
+  const LongPlan plan = long_plan(m);
+  const size_t np = n * plan.g;
+  if (!codec_chunked_ok(d))
+    return fail(D377_ERR_INIT, "residency of %s does not match the lane sets of the scratch areas", "k_compress_chunked");
+  GuardScope vb{d.vb_guard, s};                              // the lane-set areas, the table scratch, the partials: queue behind their last user
+  int rc;
+  if (partial_records(n, plan.g) * 128 > d.bml_cap && ScratchGuard::capturing(s))
+    return fail(D377_ERR_ARG, "%s", "batch_msm_long: the partial sums' area must grow, which cannot happen inside a stream capture");
+  if ((rc = ensure_partials(d, partial_records(n, plan.g) * 128))) return rc;
+  uint64_t* partials = reinterpret_cast<uint64_t*>(d.bml_partials);
+  uint64_t* half[2] = {partials + np * 16, partials + (np + n * fold_out(plan.g)) * 16};
+  const size_t places = (size_t)d.cus * WAVES_PER_SIMD;
+  auto deal = [&](size_t count, int& grid) {                 // the chunks of a lane-set kernel over `count` elements (as batch_msm_launch)
+    const ChunkDeal c = deal_chunks((count + BLOCK - 1) / BLOCK, places, (size_t)DCB_K, (size_t)d.cus * 64);
+    DcbScratch dcb{d.dcb_scratch, d.slot_pool, d.cus * WAVES_PER_SIMD, (int)c.per_lane, d.dcb_sets * BLOCK, (int)c.extra, d.pool_health};
+    dcb.prio = c.nchunks <= 2 * places ? 1 : 0;
+    grid = (int)c.nchunks;
+    return dcb;
+  };
+
+  // ---- phase 1: the chains.  The route by the number of PARTIAL sums, batch_msm_launch's rule: up to four per SIMD a wave each
+  const size_t wave_max = 4 * (size_t)d.tuned(D377_TUNE_TINY_MAX, (long long)d.cus * 4);
+  if (np <= wave_max) {
+    if ((rc = vb.acquire())) return rc;
+    const size_t lds = plan.b * row::RQ_TAB_ENTRIES * RQ_WORDS * sizeof(uint32_t);
+    if (encoded) hipLaunchKernelGGL(k_msm_long_wave<true>, dim3((unsigned)np), dim3(64), lds, s, T, pts_in, scalars, plan, np, partials, status);
+    else hipLaunchKernelGGL(k_msm_long_wave<false>, dim3((unsigned)np), dim3(64), lds, s, T, pts_in, scalars, plan, np, partials, status);
+    HIP_TRY(hipGetLastError());
+  } else {
+    // residency of the lane kernel against the lane sets, once per device (as batch_msm_launch)
+    const void* fn = encoded ? reinterpret_cast<const void*>(k_msm_long_lane<true>) : reinterpret_cast<const void*>(k_msm_long_lane<false>);
+    int& lds = d.bml_lds[encoded ? 1 : 0];
+    if (lds < 0) {
+      int nb = 0;
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, 0));
+      int pad = 0;
+      if (nb > WAVES_PER_SIMD) {
+        pad = (160 * 1024) / (WAVES_PER_SIMD + 1) + 1024;
+        if (pad > 64 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, pad));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, (size_t)pad));
+      }
+      if (nb < 1 || nb > WAVES_PER_SIMD)
+        return fail(D377_ERR_INIT, "residency of %s does not match the lane sets of the scratch areas", "k_msm_long_lane");
+      lds = pad;
+    }
+    // the table scratch of the small sums' lane kernel, grown as batch_msm_launch grows it, for b terms per lane
+    const size_t need = d.resident_lanes() * (plan.b * VB_ENTRIES * VB_ENTRY_WORDS + BM_WINDOWS) * sizeof(uint32_t);
+    if (need > d.bm_cap) {
+      if (ScratchGuard::capturing(s))
+        return fail(D377_ERR_ARG, "%s", "batch_msm_long: the table scratch must grow, which cannot happen inside a stream capture");
+      if ((rc = d.vb_guard.drain())) return rc;
+      if (d.bm_scratch) HIP_TRY(hipFree(d.bm_scratch));
+      d.bm_scratch = nullptr; d.bm_cap = 0;
+      if (hipMalloc(&d.bm_scratch, need) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(D377_ERR_HIP, "%s", "batch_msm_long: hipMalloc of the table scratch failed (0.23 GB per term of a group on 256 CUs)");
+      }
+      d.bm_cap = need;
+    }
+    if ((rc = vb.acquire())) return rc;
+    int grid = 0;
+    const DcbScratch dcb = deal(np, grid);
+    uint32_t* tab = d.bm_scratch;
+    uint32_t* dig = tab + d.resident_lanes() * plan.b * VB_ENTRIES * VB_ENTRY_WORDS;
+    if (encoded)
+      hipLaunchKernelGGL(k_msm_long_lane<true>, dim3((unsigned)grid), dim3(BLOCK), lds, s, T, pts_in, scalars, plan, np, partials, status, tab, dig, dcb);
+    else
+      hipLaunchKernelGGL(k_msm_long_lane<false>, dim3((unsigned)grid), dim3(BLOCK), lds, s, T, pts_in, scalars, plan, np, partials, status, tab, dig, dcb);
+    HIP_TRY(hipGetLastError());
+  }
+
+  // ---- phase 2: fold levels until one record per sum is left; the last level writes the caller's Element records if asked
+  const uint64_t* cur = partials;
+  int turn = 0;
+  for (size_t c = plan.g; c > 1; c = fold_out(c)) {
+    const size_t oc = fold_out(c), lanes = n * oc;
+    uint64_t* dst = (oc == 1 && xyzt_out) ? xyzt_out : half[turn];
+    size_t grid = (lanes + BLOCK - 1) / BLOCK;
+    if (grid > (size_t)d.cus * 8) grid = (size_t)d.cus * 8;
+    hipLaunchKernelGGL(k_msm_long_fold, dim3((unsigned)grid), dim3(BLOCK), 0, s, cur, c, n, dst);
+    HIP_TRY(hipGetLastError());
+    cur = dst;
+    turn ^= 1;
+  }
+
+  // ---- phase 3: the sums' Encodings, in chunks with batched inversions (codec_chunked.hip)
+  int grid = 0;
+  const DcbScratch dcb = deal(n, grid);
+  if ((rc = codec_chunked_launch(d, s, false, cur, n, out32, nullptr, grid, dcb))) return rc;
+  return vb.finish();
+}
+
+// one device's slice of a host batch: copies in, kernels, copies out, synchronised (as batch_msm.hip's batch_msm_one)
+int batch_msm_long_one(DeviceState& d, bool encoded, const uint8_t* pts_in, const uint8_t* scalars, size_t m, size_t n, uint8_t* out32,
+                       uint64_t* xyzt_out, uint8_t* status) {
+  if (n == 0) return D377_OK;
+  HIP_TRY(hipSetDevice(d.id));
+  int rc = D377_OK;
+  SyncOnError guard{&rc, d.id, d.stream, nullptr};
+  auto body = [&]() -> int {
+    const size_t rec = encoded ? 32 : 128, terms = n * m;
+    int r;
+    if ((r = ensure(d, 0, terms * rec))) return r;
+    if ((r = ensure(d, 1, terms * 32))) return r;
+    if ((r = ensure(d, 2, n * (xyzt_out ? 32 + 128 : 32)))) return r;      // the Encodings, then the Element records
+    if (encoded && (r = ensure(d, 3, terms))) return r;
+    StarveCheck starve{d, d.stream};
+    if ((r = starve.before())) return r;
+    HIP_TRY(hipMemcpyAsync(d.buf[0], pts_in, terms * rec, hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipMemcpyAsync(d.buf[1], scalars, terms * 32, hipMemcpyHostToDevice, d.stream));
+    uint64_t* xyzt_dev = xyzt_out ? reinterpret_cast<uint64_t*>(d.buf[2] + n * 32) : nullptr;
+    if ((r = batch_msm_long_launch(d, d.stream, encoded, d.buf[0], d.buf[1], m, n, d.buf[2], xyzt_dev, d.buf[3]))) return r;
+    HIP_TRY(hipMemcpyAsync(out32, d.buf[2], n * 32, hipMemcpyDeviceToHost, d.stream));
+    if (xyzt_out) HIP_TRY(hipMemcpyAsync(xyzt_out, xyzt_dev, n * 128, hipMemcpyDeviceToHost, d.stream));
+    if (encoded) HIP_TRY(hipMemcpyAsync(status, d.buf[3], terms, hipMemcpyDeviceToHost, d.stream));
+    if ((r = starve.after())) return r;
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    return starve.verdict();
+  };
+  rc = body();
+  return rc;
+}
+
+// host pointers.  The checks come in the documented order -- m, null buffers (n > 0), ctx -- and before any device is touched.
+int batch_msm_long_host(d377_ctx* ctx, bool encoded, const void* pts_in, const uint8_t* scalars, size_t m, size_t n, uint8_t* out32,
+                        uint64_t* xyzt_out, uint8_t* status) {
+  if (m < 1 || m > BML_MAX)
+    return fail_size(D377_ERR_ARG, "batch_msm_long: m = %zu: 1 .. 4096 terms per sum (D377_BATCH_MSM_LONG_MAX_TERMS); d377_msm for longer sums", m);
+  if (n) {
+    if (!pts_in) return fail(D377_ERR_ARG, "batch_msm_long: null buffer: %s", encoded ? "enc32" : "xyzt");
+    if (!scalars) return fail(D377_ERR_ARG, "batch_msm_long: null buffer: %s", "scalar32");
+    if (!out32) return fail(D377_ERR_ARG, "batch_msm_long: null buffer: %s", "enc32_out");
+    if (encoded && !status) return fail(D377_ERR_ARG, "batch_msm_long: null buffer: %s", "status");
+  }
+  if (!ctx) return fail(D377_ERR_ARG, "%s", "batch_msm_long: null context (ctx)");
+  if (n == 0) return D377_OK;
+  if (m <= BML_GROUP_MAX)                                     // one chain per sum: the small sums' call, the same bytes
+    return encoded ? d377_batch_msm_small_encoded(ctx, (const uint8_t*)pts_in, scalars, m, n, out32, xyzt_out, status)
+                   : d377_batch_msm_small(ctx, (const uint64_t*)pts_in, scalars, m, n, out32, xyzt_out);
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  const size_t nd = ctx->devs.size(), rec = encoded ? 32 : 128;
+  if (nd == 1) return batch_msm_long_one(ctx->devs[0], encoded, (const uint8_t*)pts_in, scalars, m, n, out32, xyzt_out, status);
+  // contiguous slices of the SUMS over the context's devices, one host thread per device (as batch_msm_host)
+  const size_t per = (n + nd - 1) / nd;
+  std::vector<int> rcs(nd, D377_OK);
+  std::vector<std::string> errs(nd);
+  std::vector<std::thread> workers;
+  const int delay = debug_device_delay_ms();
+  for (size_t k = 0; k < nd; ++k) {
+    const size_t lo = per * k;
+    if (lo >= n) break;
+    const size_t cnt = (lo + per <= n) ? per : n - lo;
+    workers.emplace_back([&, k, lo, cnt]() {
+      if (delay > 0) std::this_thread::sleep_for(std::chrono::milliseconds(delay));
+      rcs[k] = batch_msm_long_one(ctx->devs[k], encoded, (const uint8_t*)pts_in + lo * m * rec, scalars + lo * m * 32, m, cnt, out32 + lo * 32,
+                                  xyzt_out ? xyzt_out + lo * 16 : nullptr, encoded ? status + lo * m : nullptr);
+      if (rcs[k] != D377_OK) errs[k] = d377_g_err;
+    });
+  }
+  for (auto& w : workers) w.join();
+  for (size_t k = 0; k < nd; ++k)
+    if (rcs[k] != D377_OK) return fail(rcs[k], "%s", errs[k].c_str());
+  return D377_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int d377_batch_msm_long(d377_ctx* ctx, const uint64_t* xyzt, const uint8_t* scalar32, size_t m, size_t n, uint8_t* enc32_out,
+                        uint64_t* xyzt_out) {
+  return batch_msm_long_host(ctx, false, xyzt, scalar32, m, n, enc32_out, xyzt_out, nullptr);
+}
+int d377_batch_msm_long_encoded(d377_ctx* ctx, const uint8_t* enc32, const uint8_t* scalar32, size_t m, size_t n, uint8_t* enc32_out,
+                                uint64_t* xyzt_out, uint8_t* status) {
+  return batch_msm_long_host(ctx, true, enc32, scalar32, m, n, enc32_out, xyzt_out, status);
+}
+
+}  // extern "C"

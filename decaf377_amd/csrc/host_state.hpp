@@ -108,6 +108,9 @@ struct DeviceState {
   uint32_t* bm_scratch = nullptr;        // batch_msm.hip: tables and digit words of the batched small sums, per resident lane; grown on first use
   size_t bm_cap = 0;
   int bm_lds[2] = {-1, -1};              // batch_msm.hip: LDS padding of its lane kernel (Element / Encoding form), -1 = not asked yet
+  uint8_t* bml_partials = nullptr;       // batch_msm_long.hip: the chains' partial sums and the fold levels' records; grown on demand, never shrunk
+  size_t bml_cap = 0;
+  int bml_lds[2] = {-1, -1};             // batch_msm_long.hip: LDS padding of its lane kernel (Element / Encoding form), -1 = not asked yet
   int fx_lds[4] = {-1, -1, -1, -1};      // fixed_bases.hip: LDS padding of its lane kernel per comb width (8 / 12 / 16 / 18), -1 = not asked yet
   int fxi_lds[4] = {-1, -1, -1, -1};     // the same for the lane kernel of the indexed sums
   uint32_t* gtab = nullptr;

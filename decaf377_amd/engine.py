@@ -514,6 +514,58 @@ class Context:
         _native.check(getattr(self._lib, name)(self._h, p(pts), p(sc), ctypes.c_size_t(m), ctypes.c_size_t(n), *ptrs))
         return tuple(outs) if len(outs) > 1 else outs[0]
 
+    def msm_long(self, points, scalar32, m, outs=None, elements=False):
+        """n independent multiscalar sums of m terms each, 1 <= m <= 4096 (d377_batch_msm_long[_encoded]): msm_small's sums
+        at medium length -- every sum cut into Straus chains of at most 8 terms whose partial sums are folded on the device.
+        points: [n * m, 16] u64 Elements or [n * m, 32] u8 Encodings (detected by the row width, as msm_small does),
+        scalar32: [n * m, 32], term-major within a sum.  Returns what msm_small returns: enc [n, 32] for Elements, (enc,
+        status [n * m]) for Encodings; with elements=True (enc, xyzt [n, 16]) / (enc, xyzt, status).  outs: the same tuple
+        of preallocated arrays.  The call is host-pointer only: torch tensors are staged through host memory (the results
+        come back on the points' device).  For ONE long sum use msm()."""
+        m = int(m)
+        if points.ndim != 2 or int(points.shape[1]) not in (16, 32):
+            raise ValueError("msm_long: points must be [n * m, 16] Elements or [n * m, 32] Encodings")
+        encoded = int(points.shape[1]) == 32
+        terms = _rows(points)
+        if m < 1 or terms % m:
+            raise ValueError("msm_long: the number of points must be a multiple of m")
+        n = terms // m
+        _check(points, ENC if encoded else ELEM, terms, "msm_long points")
+        _check(scalar32, ENC, terms, "msm_long scalars", points.device if _is_torch(points) else None)
+        name = "d377_batch_msm_long_encoded" if encoded else "d377_batch_msm_long"
+        specs = [(ENC, n)] + ([(ELEM, n)] if elements else []) + ([(FLAG, terms)] if encoded else [])
+        if outs is not None and len(outs) != len(specs):
+            raise ValueError("msm_long: %d output arrays expected" % len(specs))
+        torch_in = _is_torch(points)
+        if torch_in:
+            dev = points.device
+            self._dev_index(dev)
+            if outs is not None:
+                for a, (spec, rows) in zip(outs, specs):
+                    _check(a, spec, rows, "msm_long output", dev)
+            pts = points.detach().cpu().numpy()
+            pts = pts.view(np.uint64) if pts.dtype == np.int64 else pts
+            sc = scalar32.detach().cpu().numpy()
+            host = [np.zeros((rows,) + tail, np.uint8 if k == "u8" else np.uint64) for (tail, k), rows in specs]
+        else:
+            pts, sc = points, scalar32
+            host = outs if outs is not None else [np.zeros((rows,) + tail, np.uint8 if k == "u8" else np.uint64) for (tail, k), rows in specs]
+        pts, sc = np.ascontiguousarray(pts), np.ascontiguousarray(sc)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        ptrs = [p(o) for o in host]
+        if not elements:
+            ptrs.insert(1, ctypes.c_void_p(None))
+        _native.check(getattr(self._lib, name)(self._h, p(pts), p(sc), ctypes.c_size_t(m), ctypes.c_size_t(n), *ptrs))
+        if torch_in:
+            import torch
+            res = [torch.from_numpy(h.view(np.int64) if h.dtype == np.uint64 else h).to(dev) for h in host]
+            if outs is not None:
+                for o, r in zip(outs, res):
+                    o.copy_(r)
+                res = list(outs)
+            return tuple(res) if len(res) > 1 else res[0]
+        return tuple(host) if len(host) > 1 else host[0]
+
     def msm(self, points, scalar32, encoded=None):
         """Element::vartime_multiscalar_mul (src/ark_curve/element/projective.rs:99-117).
         points: [n, 16] u64 Elements or [n, 32] u8 Encodings (detected by the row width).

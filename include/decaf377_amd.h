@@ -301,6 +301,37 @@ int d377_batch_msm_small(d377_ctx* ctx, const uint64_t* xyzt, const uint8_t* sca
 int d377_batch_msm_small_encoded(d377_ctx* ctx, const uint8_t* enc32, const uint8_t* scalar32, size_t m, size_t n,
                                  uint8_t* enc32_out, uint64_t* xyzt_out, uint8_t* status);
 
+/* MANY multiscalar sums of medium length at once: the same sums as d377_batch_msm_small[_encoded], with
+ * 1 <= m <= D377_BATCH_MSM_LONG_MAX_TERMS terms per sum -- Pedersen vector commitments to a thousand vectors of 256 entries,
+ * the rounds of an inner-product argument, many batches of verification equations.  The semantics are exactly those of the
+ * small sums: points and scalars are n x m records, term-major within a sum; enc32_out[i] = the canonical Encoding of sum i;
+ * xyzt_out (optional) = the sums as Element records (some extended representative); _encoded reports invalid Encodings in
+ * status[i m + j] and leaves them out of their sum; a record with Z = 0 counts as the identity; scalars are any 32 bytes,
+ * reduced mod r.  The length is UNIFORM: a caller with shorter sums pads them with zero scalars or Z = 0 records, which
+ * contribute nothing (and cost as much as a present term).
+ * Cost model: a sum is cut into g = ceil(m / 8) groups of b = ceil(m / g) terms, each group is one Straus chain of the small
+ * sums (252 doublings + 64 b additions + b tables), and the g partial sums are added on the device, 16 per lane and level
+ * (at most three levels), before ONE compressor pass, no host round trips (by instruction count, an estimate that was not
+ * measured: about 8 % more than m / 8 eight-term chains).  Up to four chains per SIMD run a wave each, beyond that a lane each.
+ * Measured on one MI355X, host arrays, 2^20 terms per call (profiles/batch_msm_long_bench.json): 10.2 ms at (n, m) =
+ * (2^16, 16), (2^12, 256) and (2^8, 4096) alike, against 18.1 / 21.7 / 21.9 ms for the composition through host memory
+ * (d377_batch_msm_small on groups of 8, rounds of d377_batch_add, d377_batch_compress: x 1.8 / 2.1 / 2.1) and 18.4 s / 1.34 s /
+ * 123 ms for n calls of d377_msm (scaled from 128 calls).  For m <= 8 the call forwards to d377_batch_msm_small[_encoded] (the
+ * same bytes).  For ONE long sum use d377_msm: measured at (1, 4096), 0.97 ms here against 0.48 ms for d377_msm (the
+ * composition: 1.31 ms) -- a single sum is 512 chains on 512 waves of a chip that holds thousands, as long as one chain plus
+ * three fold levels and a compressor pass, while the Pippenger MSM needs fewer additions (by count about a third: an
+ * estimate).  Scratch: the small sums' table scratch for b terms, and 128 bytes per group, grown on demand and kept (a failed
+ * allocation is D377_ERR_HIP and leaves nothing half-allocated).
+ * Arguments are checked in this order, the first two before any device is touched: m (0 or more than 4096 is D377_ERR_ARG,
+ * the message names m), null buffers when n > 0, ctx; n == 0 with good arguments is D377_OK.  A multi-GPU context slices the
+ * SUMS over its devices.  Host pointers only: a device-pointer form is not offered (a Python torch tensor is staged through
+ * host memory). */
+#define D377_BATCH_MSM_LONG_MAX_TERMS 4096
+int d377_batch_msm_long(d377_ctx* ctx, const uint64_t* xyzt, const uint8_t* scalar32, size_t m, size_t n, uint8_t* enc32_out,
+                        uint64_t* xyzt_out);
+int d377_batch_msm_long_encoded(d377_ctx* ctx, const uint8_t* enc32, const uint8_t* scalar32, size_t m, size_t n,
+                                uint8_t* enc32_out, uint64_t* xyzt_out, uint8_t* status);
+
 /* Fixed-base combs for caller-chosen points, and many sums over them.  The reference reaches this through arkworks:
  * Element implements ScalarMul / VariableBaseMSM / CurveGroup (src/ark_curve/element.rs:22-38), so ark-ec's FixedBase
  * window tables work on any Element -- a Pedersen commitment v G + r H, a value commitment's asset and blinding generators.

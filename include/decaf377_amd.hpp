@@ -388,6 +388,30 @@ class Engine {
     if (encodings) *encodings = std::move(enc);
     return {out, results(points, st)};
   }
+  /// MANY sums of medium length at once: the sums of vartime_multiscalar_mul_batch with 1 <= m <= 4096 terms each
+  /// (d377_batch_msm_long: every sum cut into chains of at most 8 terms, the partial sums folded on the device).  Host
+  /// vectors only; for ONE long sum use vartime_multiscalar_mul.
+  std::vector<Element> vartime_multiscalar_mul_batch_long(size_t m, const std::vector<Fr>& scalars, const std::vector<Element>& points,
+                                                          std::vector<Encoding>* encodings = nullptr) {
+    if (scalars.size() != points.size() || m == 0 || points.size() % m) throw std::invalid_argument("length mismatch");
+    std::vector<Element> out(points.size() / m);
+    std::vector<Encoding> enc(out.size());
+    check(d377_batch_msm_long(ctx_, u64(points), u8(scalars), m, out.size(), u8m(enc), reinterpret_cast<uint64_t*>(out.data())));
+    if (encodings) *encodings = std::move(enc);
+    return out;
+  }
+  /// The same over Encodings: an invalid one is reported (Err, per term) and left out of its sum.
+  std::pair<std::vector<Element>, std::vector<Result<Encoding>>> vartime_multiscalar_mul_batch_long_encoded(
+      size_t m, const std::vector<Fr>& scalars, const std::vector<Encoding>& points, std::vector<Encoding>* encodings = nullptr) {
+    if (scalars.size() != points.size() || m == 0 || points.size() % m) throw std::invalid_argument("length mismatch");
+    std::vector<Element> out(points.size() / m);
+    std::vector<Encoding> enc(out.size());
+    std::vector<uint8_t> st(points.size() ? points.size() : 1);
+    check(d377_batch_msm_long_encoded(ctx_, u8(points), u8(scalars), m, out.size(), u8m(enc), reinterpret_cast<uint64_t*>(out.data()), st.data()));
+    st.resize(points.size());
+    if (encodings) *encodings = std::move(enc);
+    return {out, results(points, st)};
+  }
   /// CurveGroup::normalize_batch (src/ark_curve/element.rs:74-81): affine (x, y) as 4 Montgomery limbs each
   std::vector<std::array<uint64_t, 8>> normalize_batch(const std::vector<Element>& p) {
     std::vector<std::array<uint64_t, 8>> out(p.size());

@@ -454,6 +454,39 @@ impl Element {
         })?;
         Ok((out.chunks_exact(16).map(element_from_xyzt).collect(), enc, results(&st, |_| ())))
     }
+    /// MANY sums of medium length at once: the sums of `vartime_multiscalar_mul_batch_gpu` with `m` terms each (1..=4096),
+    /// every sum cut into Straus chains of at most 8 terms whose partial sums are folded on the GPU (d377_batch_msm_long).
+    /// Host slices only; for ONE long sum use `vartime_multiscalar_mul_gpu`.
+    pub fn vartime_multiscalar_mul_batch_long_gpu(ctx: &GpuContext, m: usize, scalars: &[Fr], points: &[Element])
+        -> Result<(Vec<Element>, Vec<Encoding>), GpuError> {
+        assert_eq!(scalars.len(), points.len());
+        assert!(m >= 1 && points.len() % m == 0);
+        let n = points.len() / m;
+        let xyzt = elements_to_xyzt(points);
+        let bytes = pack32(scalars, |k| k.to_bytes());
+        let mut enc = vec![Encoding([0u8; 32]); n];
+        let mut out = vec![0u64; 16 * n];
+        check(unsafe {
+            ffi::d377_batch_msm_long(ctx.0, xyzt.as_ptr(), bytes.as_ptr(), m, n, enc.as_mut_ptr() as *mut u8, out.as_mut_ptr())
+        })?;
+        Ok((out.chunks_exact(16).map(element_from_xyzt).collect(), enc))
+    }
+    /// The same over Encodings: an invalid one is reported (per term) and left out of its sum.
+    pub fn vartime_multiscalar_mul_batch_long_encoded_gpu(ctx: &GpuContext, m: usize, scalars: &[Fr], points: &[Encoding])
+        -> Result<(Vec<Element>, Vec<Encoding>, Vec<Result<(), EncodingError>>), GpuError> {
+        assert_eq!(scalars.len(), points.len());
+        assert!(m >= 1 && points.len() % m == 0);
+        let n = points.len() / m;
+        let bytes = pack32(scalars, |k| k.to_bytes());
+        let mut enc = vec![Encoding([0u8; 32]); n];
+        let mut out = vec![0u64; 16 * n];
+        let mut st = vec![0u8; points.len()];
+        check(unsafe {
+            ffi::d377_batch_msm_long_encoded(ctx.0, enc_ptr(points), bytes.as_ptr(), m, n, enc.as_mut_ptr() as *mut u8, out.as_mut_ptr(),
+                                             st.as_mut_ptr())
+        })?;
+        Ok((out.chunks_exact(16).map(element_from_xyzt).collect(), enc, results(&st, |_| ())))
+    }
 }
 
 // ---- Fq / Fr -----------------------------------------------------------------------------------
