@@ -41,14 +41,15 @@ constexpr int BM_MAX = D377_BATCH_MSM_MAX_TERMS;
 static_assert(BM_MAX == 8, "a window's digits of the m points of a sum are the eight nibbles of one word");
 static_assert(VB_ENTRIES == 9, "straus_sum stores entries 0 .. 8 of every point's table");
 
-// Scratch of one resident lane: tables [point][entry][lane] as k_scalar_mul_var's (a wave stores one entry as 12 KiB
+// Scratch of one resident lane: tables [point][entry][lane] of four 12-word limb slots (BM_ENTRY_WORDS, 192 bytes: the
+// layout k_scalar_mul_var had before its entries became 128-byte packed records; a wave stores one entry as 12 KiB
 // contiguous; a negative digit swaps the ypx / ymx slots by address), and the digit words [window][lane]: nibble p of word w =
 // the signed digit of point p in window w.
 struct StrausTab {
   uint32_t* tab;
   uint32_t* dig;
   size_t nthreads, tid;
-  __device__ __forceinline__ uint32_t* entry(int p, int j) const { return tab + (((size_t)p * VB_ENTRIES + j) * nthreads + tid) * VB_ENTRY_WORDS; }
+  __device__ __forceinline__ uint32_t* entry(int p, int j) const { return tab + (((size_t)p * VB_ENTRIES + j) * nthreads + tid) * BM_ENTRY_WORDS; }
   __device__ __forceinline__ void store(int p, int j, const gec& c) {
     uint32_t* q = entry(p, j);
     slot_store(q, c.ypx); slot_store(q + SLOT, c.ymx); slot_store(q + 2 * SLOT, c.z2); slot_store(q + 3 * SLOT, c.kt);
@@ -191,7 +192,7 @@ k_batch_msm_wave(SqrtTables T, const void* pts_in, const uint8_t* scalar32, int 
 // ------------------------------------------------------------------------------ host side ---
 // bytes of scratch per resident lane for sums of m terms
 size_t scratch_bytes(const DeviceState& d, int m) {
-  return d.resident_lanes() * ((size_t)m * VB_ENTRIES * VB_ENTRY_WORDS + BM_WINDOWS) * sizeof(uint32_t);
+  return d.resident_lanes() * ((size_t)m * VB_ENTRIES * BM_ENTRY_WORDS + BM_WINDOWS) * sizeof(uint32_t);
 }
 
 // everything on device pointers, enqueued on `s`; the caller holds ctx->mu
@@ -247,7 +248,7 @@ int batch_msm_launch(DeviceState& d, hipStream_t s, bool encoded, const void* pt
   DcbScratch dcb{d.dcb_scratch, d.slot_pool, d.cus * WAVES_PER_SIMD, (int)c.per_lane, d.dcb_sets * BLOCK, (int)c.extra, d.pool_health};
   dcb.prio = c.nchunks <= 2 * places ? 1 : 0;               // as d377.hip's chunks_of
   uint32_t* tab = d.bm_scratch;
-  uint32_t* dig = tab + d.resident_lanes() * (size_t)m * VB_ENTRIES * VB_ENTRY_WORDS;
+  uint32_t* dig = tab + d.resident_lanes() * (size_t)m * VB_ENTRIES * BM_ENTRY_WORDS;
   if (encoded)
     hipLaunchKernelGGL(k_batch_msm_lane<true>, dim3((unsigned)c.nchunks), dim3(BLOCK), lds, s, T, pts_in, scalars, (int)m, n, out32, xyzt_out, status, tab, dig, dcb);
   else

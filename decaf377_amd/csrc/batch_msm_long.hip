@@ -54,7 +54,7 @@ struct StrausTab {
   uint32_t* tab;
   uint32_t* dig;
   size_t nthreads, tid;
-  __device__ __forceinline__ uint32_t* entry(int p, int j) const { return tab + (((size_t)p * VB_ENTRIES + j) * nthreads + tid) * VB_ENTRY_WORDS; }
+  __device__ __forceinline__ uint32_t* entry(int p, int j) const { return tab + (((size_t)p * VB_ENTRIES + j) * nthreads + tid) * BM_ENTRY_WORDS; }
   __device__ __forceinline__ void store(int p, int j, const gec& c) {
     uint32_t* q = entry(p, j);
     slot_store(q, c.ypx); slot_store(q + SLOT, c.ymx); slot_store(q + 2 * SLOT, c.z2); slot_store(q + 3 * SLOT, c.kt);
@@ -292,7 +292,7 @@ int batch_msm_long_launch(DeviceState& d, hipStream_t s, bool encoded, const voi
       lds = pad;
     }
     // the table scratch of the small sums' lane kernel, grown as batch_msm_launch grows it, for b terms per lane
-    const size_t need = d.resident_lanes() * (plan.b * VB_ENTRIES * VB_ENTRY_WORDS + BM_WINDOWS) * sizeof(uint32_t);
+    const size_t need = d.resident_lanes() * (plan.b * VB_ENTRIES * BM_ENTRY_WORDS + BM_WINDOWS) * sizeof(uint32_t);
     if (need > d.bm_cap) {
       if (ScratchGuard::capturing(s))
         return fail(D377_ERR_ARG, "%s", "batch_msm_long: the table scratch must grow, which cannot happen inside a stream capture");
@@ -309,7 +309,7 @@ int batch_msm_long_launch(DeviceState& d, hipStream_t s, bool encoded, const voi
     int grid = 0;
     const DcbScratch dcb = deal(np, grid);
     uint32_t* tab = d.bm_scratch;
-    uint32_t* dig = tab + d.resident_lanes() * plan.b * VB_ENTRIES * VB_ENTRY_WORDS;
+    uint32_t* dig = tab + d.resident_lanes() * plan.b * VB_ENTRIES * BM_ENTRY_WORDS;
     if (encoded)
       hipLaunchKernelGGL(k_msm_long_lane<true>, dim3((unsigned)grid), dim3(BLOCK), lds, s, T, pts_in, scalars, plan, np, partials, status, tab, dig, dcb);
     else

@@ -35,30 +35,39 @@ thread_local char d377_g_err[512] = "";
 namespace {
 
 // per-lane window table of the variable-base kernel in global scratch, laid out
-// [entry][thread][4 slots x 12 words]: a wave stores one entry as 12 KiB contiguous, and a lane
-// fetches its 192-byte (three 64-B sectors) record with 16-byte loads.  A negative digit
-// swaps the ypx / ymx slots by address.  F: the field type of the chain that uses it (fes: the signed window loop,
-// same records bit for bit).  Entry 0, the cached identity, is one constant record per device (DeviceState::vb_identity,
-// written once by k_init_vb_identity): no lane stores it, load(0, .) takes the shared record by address select, and the
-// lanes' own slots 0 of the scratch stay unused.
+// [entry][thread][4 slots x 8 words]: an entry is 128 bytes, 128-byte aligned -- one cache line, which a lane fetches
+// with eight 16-byte loads and a wave stores as 8 KiB contiguous.  A slot holds the field value as a 256-bit integer
+// (device_util.hpp: slot_pack_store / slot_unpack_load; fqs29.hpp: fes_pack256), not a limb vector: nine padded limbs
+// made the entry 192 bytes, three sectors across two lines.  A negative digit swaps the ypx / ymx slots by address.
+// F: the field type of the chain that uses it (fes: the signed window loop).  Entry 0, the cached identity, is one
+// constant record per device (DeviceState::vb_identity, written once by k_init_vb_identity in the same packed form): no
+// lane stores it, load(0, .) takes the shared record by address select, and the lanes' own slots 0 of the scratch stay
+// unused.
 template <class F>
 struct GlobalTab {
+  static_assert(std::is_same<F, fes>::value, "the packed slots hold signed-limb elements");
   static constexpr bool shared_identity = true;         // curve.hpp, ge_scalar_mul_w4: entry 0 is never stored
   uint32_t* base;
   const uint32_t* ident;
   size_t nthreads, tid;
+  // Unlike the limb slots this replaces, the packed slot is NOT lossless: fes_pack256 reduces with + 9q or - 4q picked
+  // by the top limb, which is right only for a value in (-8.7q, 17.4q) whose limbs 0..7 stay below 2^30 in magnitude.
+  // Every entry ge_scalar_mul_w4 stores meets that (a product, a sum or difference of two products, or sums of the
+  // carried coordinates of the point: fqs29.hpp); only the -DD377_BOUNDS host build checks it, a device build would wrap
+  // silently.  A new caller that stores anything else must carry it first.
   __device__ __forceinline__ void store(int j, const gec_of<F>& c) {
     uint32_t* p = base + ((size_t)j * nthreads + tid) * VB_ENTRY_WORDS;
-    slot_store(p, c.ypx); slot_store(p + SLOT, c.ymx); slot_store(p + 2 * SLOT, c.z2); slot_store(p + 3 * SLOT, c.kt);
+    slot_pack_store(p, c.ypx); slot_pack_store(p + PACKED_SLOT, c.ymx);
+    slot_pack_store(p + 2 * PACKED_SLOT, c.z2); slot_pack_store(p + 3 * PACKED_SLOT, c.kt);
   }
   __device__ __forceinline__ gec_of<F> load(int j, bool swap) const {
     const uint32_t* own = base + ((size_t)j * nthreads + tid) * VB_ENTRY_WORDS;
     const uint32_t* p = j == 0 ? ident : own;
     gec_of<F> c;
-    c.ypx = slot_load_as<F>(p + (swap ? SLOT : 0));
-    c.ymx = slot_load_as<F>(p + (swap ? 0 : SLOT));
-    c.z2 = slot_load_as<F>(p + 2 * SLOT);
-    c.kt = slot_load_as<F>(p + 3 * SLOT);
+    c.ypx = slot_unpack_load<F>(p + (swap ? PACKED_SLOT : 0));
+    c.ymx = slot_unpack_load<F>(p + (swap ? 0 : PACKED_SLOT));
+    c.z2 = slot_unpack_load<F>(p + 2 * PACKED_SLOT);
+    c.kt = slot_unpack_load<F>(p + 3 * PACKED_SLOT);
     return c;
   }
 };
@@ -102,7 +111,8 @@ __global__ void __launch_bounds__(BLOCK) k_init_gtab(uint32_t* gtab) {
 __global__ void k_init_vb_identity(uint32_t* rec) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   const gec_of<fes> id = gec_identity<fes>();
-  slot_store(rec, id.ypx); slot_store(rec + SLOT, id.ymx); slot_store(rec + 2 * SLOT, id.z2); slot_store(rec + 3 * SLOT, id.kt);
+  slot_pack_store(rec, id.ypx); slot_pack_store(rec + PACKED_SLOT, id.ymx);
+  slot_pack_store(rec + 2 * PACKED_SLOT, id.z2); slot_pack_store(rec + 3 * PACKED_SLOT, id.kt);
 }
 
 // s_lookup: keys g^-(nu * 2^39) (invsqrt.rs:27-39) in both tight representations -> nu.
@@ -1492,6 +1502,9 @@ int init_device(DeviceState& d) {
 
   HIP_TRY(hipMalloc(&d.vb_scratch, (size_t)d.vb_blocks * BLOCK * VB_ENTRIES * VB_ENTRY_WORDS * sizeof(uint32_t)));
   HIP_TRY(hipMalloc(&d.vb_identity, VB_ENTRY_WORDS * sizeof(uint32_t)));
+  if (((uintptr_t)d.vb_scratch | (uintptr_t)d.vb_identity) % (VB_ENTRY_WORDS * sizeof(uint32_t)) != 0) {
+    return ::d377::fail(D377_ERR_INIT, "variable-base window tables: %s", "the scratch is not aligned to its 128-byte entries");
+  }
   hipLaunchKernelGGL(k_init_vb_identity, dim3(1), dim3(64), 0, d.stream, d.vb_identity);
   HIP_TRY(hipGetLastError());
   // round records of the batched inversions: DCB_SLOTS x DCB_KMAX 32-byte records per lane of every lane set (480 MiB), and the

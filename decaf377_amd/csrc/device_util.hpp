@@ -14,7 +14,9 @@ constexpr int BLOCK = 256;
 constexpr int WAVES_PER_SIMD = D377_WAVES_PER_SIMD;   // occupancy the kernels are built for (VGPR budget 512 / this; LDS = POW_TAB * 9 KiB per block)
 constexpr int SLOT = 12;                     // one field element slot in a table entry: 9 limbs + 3 pad = 3 x 16 B
 constexpr int VB_ENTRIES = 9;                // cached 0..8 times P
-constexpr int VB_ENTRY_WORDS = 4 * SLOT;     // ypx, ymx, z2, kt: 192 B, 64-B aligned
+constexpr int PACKED_SLOT = PACKED_WORDS;    // one field element as a 256-bit integer (fqs29.hpp): 2 x 16 B
+constexpr int VB_ENTRY_WORDS = 4 * PACKED_SLOT;   // variable-base window table: ypx, ymx, z2, kt packed, 128 B = one line, 128-B aligned
+constexpr int BM_ENTRY_WORDS = 4 * SLOT;     // the small sums' window tables (batch_msm*.hip): four limb slots, 192 B
 constexpr int AP_WORDS = 32;                 // affine cached point record: ypx, ymx, kt = 27 limbs in a 128-byte, 128-byte-aligned slot
 constexpr int FBW_ENTRY_WORDS = AP_WORDS;    // fixed-base comb entries are such records
 
@@ -92,6 +94,23 @@ template <> __device__ __forceinline__ fes slot_load_as<fes>(const uint32_t* p) 
 #pragma unroll
   for (int i = 0; i < NL; ++i) r.l[i] = (int32_t)u.l[i];
   return r;
+}
+
+// The packed 32-byte slot of the variable-base window table (d377.hip GlobalTab): the value as a 256-bit integer, two
+// 16-byte stores / loads.  The arithmetic is fqs29.hpp's fes_pack256 / fes_unpack256, which the host builds walk.
+__device__ __forceinline__ void slot_pack_store(uint32_t* p, const fes& v) {
+  uint32_t w[PACKED_SLOT];
+  fes_pack256(v, w);
+  uint4* q = reinterpret_cast<uint4*>(p);
+  q[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  q[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+template <class F> __device__ __forceinline__ F slot_unpack_load(const uint32_t* p);
+template <> __device__ __forceinline__ fes slot_unpack_load<fes>(const uint32_t* p) {
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+  const uint4 a = q[0], b = q[1];
+  const uint32_t w[PACKED_SLOT] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  return fes_unpack256(w);
 }
 
 // Cached AFFINE point record: Y+X, Y-X (both carried: a negative digit swaps them), 2dXY -- 27 limbs packed into a

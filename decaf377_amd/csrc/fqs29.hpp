@@ -270,4 +270,75 @@ D377_HD fe fe_unsigned(const fes& a) {
   return fe_carry(t);
 }
 
+// ---- the 256-bit packed form (the variable-base window table's slots: device_util.hpp, d377.hip GlobalTab) ----------
+// A table slot holds the element's value as one little-endian integer in [0, 2^256 = 13.7q): 8 words, so that the four
+// slots of an entry fill exactly one 128-byte line.  Packing brings the value v into that range by adding 9q or -4q,
+// chosen by the top limb alone.  A table entry is a product, a sum or a difference of two products, or -- entry 1, made
+// of the point as it was decompressed or loaded -- of two carried fe coordinates (below 8.7q each), so v lies in
+// (-8.7q, 17.4q); and with limbs 0..7 below 2^30 in magnitude the top limb is within 2 of v / 2^232.  Top limb below
+// PACK_BIG_TOP (v < 4.29q): + 9q, in [0, 13.3q); from there on (v > 4.28q): - 4q, in (0.28q, 13.4q).  The bounds build
+// asserts v in [-9q, 17.7q) and the limb magnitudes.  Then the one SEQUENTIAL carry of the chain leaves nine exact
+// 29-bit digits, and 9 x 29 bits are cut into 8 x 32.  Unpacking gives limbs 0..7 in [0, 2^29) and a top limb below
+// 2^24: tighter than any operand the window loop read before.
+constexpr uint32_t Q4L[NL] = {0x00000004u, 0x02300000u, 0x0000010au, 0x13b7f680u, 0x0c00566au,
+                              0x1a3cb86fu, 0x15660b44u, 0x0f4d1652u, 0x004aad95u};
+constexpr uint32_t Q9L[NL] = {0x00000009u, 0x14ec0000u, 0x00000256u, 0x1c5deaa0u, 0x1300c26fu, 0x1b089efau, 0x0025995au, 0x0a6d723au, 0x00a80690u};
+constexpr bool is_multiple_of_q(const uint32_t (&m)[NL], uint64_t k) {
+  uint64_t c = 0;
+  for (int i = 0; i < NL; ++i) {
+    const uint64_t t = k * QL[i] + c;
+    if (m[i] != (i < NL - 1 ? (t & MASK29) : t)) return false;
+    c = t >> RB;
+  }
+  return true;
+}
+static_assert(is_multiple_of_q(Q4L, 4) && is_multiple_of_q(Q9L, 9), "Q4L, Q9L must be 4q and 9q in radix 2^29");
+constexpr int PACKED_WORDS = 8;
+// the top limb at which the pack turns from + 9q to - 4q: at least 4 q / 2^232 + 3 = 4 894 105 (v - 4q >= 0 above it),
+// at most 2^24 - 9 q / 2^232 - 2 = 5 765 486 (v + 9q < 2^256 below it)
+constexpr int32_t PACK_BIG_TOP = 5 << 20;
+
+D377_HD void fes_pack256(const fes& a, uint32_t w[PACKED_WORDS]) {
+  uint32_t t[NL];
+  int32_t c = 0;
+  const bool big = a.l[NL - 1] >= PACK_BIG_TOP;
+#pragma unroll
+  for (int i = 0; i < NL - 1; ++i) {
+    const int32_t s = (int32_t)((uint32_t)a.l[i] + (big ? 0u - Q4L[i] : Q9L[i]) + (uint32_t)c);
+    t[i] = (uint32_t)s & MASK29;
+    c = s >> RB;
+  }
+  t[NL - 1] = (uint32_t)a.l[NL - 1] + (big ? 0u - Q4L[NL - 1] : Q9L[NL - 1]) + (uint32_t)c;
+#if defined(D377_BOUNDS)
+  {
+    auto sh = [](int64_t v) { return v >= 0 ? v >> RB : -((-v + MASK29) >> RB); };
+    int64_t clo = 0, chi = 0;
+    for (int i = 0; i < NL; ++i) {
+      const int64_t lo = a.lo[i] - (int64_t)Q4L[i] + clo, hi = a.hi[i] + (int64_t)Q9L[i] + chi;
+      bound_require(lo >= -((int64_t)1 << 31) && hi < ((int64_t)1 << 31), "fes pack: digit sum leaves int32");
+      if (i < NL - 1) bound_require(a.lo[i] > -((int64_t)1 << 30) && a.hi[i] < ((int64_t)1 << 30), "fes pack: a low limb may reach 2^30: the top limb no longer tells the value");
+      clo = sh(lo); chi = sh(hi);
+    }
+    bound_require(a.vlo + 9.0 >= 0.0, "fes pack: value + 9q may be negative");
+    bound_require(a.vhi - 4.0 < R_OVER_Q / 32.0, "fes pack: value - 4q may reach 2^256");
+    bound_require(t[NL - 1] < (1u << 24), "fes pack: top digit outside [0, 2^24)");   // (this input's own digit)
+  }
+#endif
+#pragma unroll
+  for (int j = 0; j < PACKED_WORDS; ++j) w[j] = (t[j] >> (3 * j)) | (t[j + 1] << (RB - 3 * j));
+}
+D377_HD fes fes_unpack256(const uint32_t w[PACKED_WORDS]) {
+  fes r;
+  r.l[0] = (int32_t)(w[0] & MASK29);
+#pragma unroll
+  for (int i = 1; i < NL - 1; ++i) r.l[i] = (int32_t)(((w[i - 1] >> (32 - 3 * i)) | (w[i] << (3 * i))) & MASK29);
+  r.l[NL - 1] = (int32_t)(w[PACKED_WORDS - 1] >> 8);
+#if defined(D377_BOUNDS)
+  for (int i = 0; i < NL - 1; ++i) { r.lo[i] = 0; r.hi[i] = MASK29; }
+  r.lo[NL - 1] = 0; r.hi[NL - 1] = (1 << 24) - 1;
+  r.vlo = 0.0; r.vhi = R_OVER_Q / 32.0;               // any value below 2^256
+#endif
+  return r;
+}
+
 }  // namespace d377

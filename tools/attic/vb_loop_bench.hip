@@ -13,11 +13,11 @@ using namespace d377;
 struct GlobalTab {
   uint32_t* base; size_t nthreads, tid;
   __device__ __forceinline__ void store(int j, const gec& c) {
-    uint32_t* p = base + ((size_t)j * nthreads + tid) * VB_ENTRY_WORDS;
+    uint32_t* p = base + ((size_t)j * nthreads + tid) * BM_ENTRY_WORDS;
     slot_store(p, c.ypx); slot_store(p + SLOT, c.ymx); slot_store(p + 2 * SLOT, c.z2); slot_store(p + 3 * SLOT, c.kt);
   }
   __device__ __forceinline__ gec load(int j, bool swap) const {
-    const uint32_t* p = base + ((size_t)j * nthreads + tid) * VB_ENTRY_WORDS;
+    const uint32_t* p = base + ((size_t)j * nthreads + tid) * BM_ENTRY_WORDS;
     gec c;
     c.ypx = slot_load(p + (swap ? SLOT : 0)); c.ymx = slot_load(p + (swap ? 0 : SLOT));
     c.z2 = slot_load(p + 2 * SLOT); c.kt = slot_load(p + 3 * SLOT);
@@ -49,7 +49,7 @@ __global__ void k_fill(uint32_t* pts, size_t n) {   // generator multiples as in
 template <int WAVES> int run(int cus, const uint32_t* pts, const uint8_t* k, size_t n, uint32_t* out) {
   uint32_t* scratch;
   const int blocks = cus * WAVES;
-  CK(hipMalloc(&scratch, (size_t)blocks * BLOCK * VB_ENTRIES * VB_ENTRY_WORDS * 4));
+  CK(hipMalloc(&scratch, (size_t)blocks * BLOCK * VB_ENTRIES * BM_ENTRY_WORDS * 4));
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   hipLaunchKernelGGL(k_loop<WAVES>, dim3(blocks), dim3(BLOCK), 0, 0, pts, k, n, out, scratch); CK(hipDeviceSynchronize());
   float best = 1e30f;

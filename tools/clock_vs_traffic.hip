@@ -1,6 +1,8 @@
 // Experiment (round 4, review item 6): does the table traffic of the variable-base window loop cost clock?
-// k_scalar_mul_var keeps a 9-entry window table per lane in global scratch and gathers one entry per window: 62 GB per
-// 2^22-element launch for 0.4 GB of algorithmic bytes, while the chip sustains 2.2-2.3 GHz under it.  Here the same loop
+// k_scalar_mul_var keeps a 9-entry window table per lane in global scratch and gathers one entry per window: with the
+// 192-byte limb-slot entries it had in round 4, 62 GB per 2^22-element launch for 0.4 GB of algorithmic bytes, while the
+// chip sustained 2.2-2.3 GHz under it.  This tool models that FORMER layout (four 12-word limb slots, BM_ENTRY_WORDS; the
+// product kernel's entries are 128-byte packed records since).  Here the same loop
 // (table build + 63 windows of 4 doublings and one addition, no square roots) runs twice, alternating on one box:
 //   gathers   the table in global scratch, as in the product kernel
 //   registers the table replaced by register-resident stand-ins (same arithmetic, no table stores or loads)
@@ -20,11 +22,11 @@ using namespace d377;
 struct GlobalTab {
   uint32_t* base; size_t nthreads, tid;
   __device__ __forceinline__ void store(int j, const gec& c) {
-    uint32_t* p = base + ((size_t)j * nthreads + tid) * VB_ENTRY_WORDS;
+    uint32_t* p = base + ((size_t)j * nthreads + tid) * BM_ENTRY_WORDS;
     slot_store(p, c.ypx); slot_store(p + SLOT, c.ymx); slot_store(p + 2 * SLOT, c.z2); slot_store(p + 3 * SLOT, c.kt);
   }
   __device__ __forceinline__ gec load(int j, bool swap) const {
-    const uint32_t* p = base + ((size_t)j * nthreads + tid) * VB_ENTRY_WORDS;
+    const uint32_t* p = base + ((size_t)j * nthreads + tid) * BM_ENTRY_WORDS;
     gec c;
     c.ypx = slot_load(p + (swap ? SLOT : 0)); c.ymx = slot_load(p + (swap ? 0 : SLOT));
     c.z2 = slot_load(p + 2 * SLOT); c.kt = slot_load(p + 3 * SLOT);
@@ -83,7 +85,7 @@ int main() {
   const int blocks = p.multiProcessorCount * 2;
   uint32_t *pts, *out, *scratch; uint8_t* k; unsigned long long* clocks;
   CK(hipMalloc(&pts, n * 192)); CK(hipMalloc(&out, n * 192)); CK(hipMalloc(&k, n * 32)); CK(hipMalloc(&clocks, 16));
-  CK(hipMalloc(&scratch, (size_t)blocks * BLOCK * VB_ENTRIES * VB_ENTRY_WORDS * 4));
+  CK(hipMalloc(&scratch, (size_t)blocks * BLOCK * VB_ENTRIES * BM_ENTRY_WORDS * 4));
   hipLaunchKernelGGL(k_fill, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, pts, n);
   std::vector<uint8_t> hk(n * 32); uint64_t s = 88172645463325252ull;
   for (auto& b : hk) { s ^= s << 13; s ^= s >> 7; s ^= s << 17; b = (uint8_t)s; }

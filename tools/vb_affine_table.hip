@@ -24,11 +24,11 @@ constexpr int CHUNK_E = 8;                       // elements per lane per shared
 struct GlobalTab {
   uint32_t* base; size_t nthreads, tid;
   __device__ __forceinline__ void store(int j, const gec& c) {
-    uint32_t* p = base + ((size_t)j * nthreads + tid) * VB_ENTRY_WORDS;
+    uint32_t* p = base + ((size_t)j * nthreads + tid) * BM_ENTRY_WORDS;
     slot_store(p, c.ypx); slot_store(p + SLOT, c.ymx); slot_store(p + 2 * SLOT, c.z2); slot_store(p + 3 * SLOT, c.kt);
   }
   __device__ __forceinline__ gec load(int j, bool swap) const {
-    const uint32_t* p = base + ((size_t)j * nthreads + tid) * VB_ENTRY_WORDS;
+    const uint32_t* p = base + ((size_t)j * nthreads + tid) * BM_ENTRY_WORDS;
     gec c;
     c.ypx = slot_load(p + (swap ? SLOT : 0)); c.ymx = slot_load(p + (swap ? 0 : SLOT));
     c.z2 = slot_load(p + 2 * SLOT); c.kt = slot_load(p + 3 * SLOT);
@@ -147,7 +147,7 @@ int main() {
   const size_t lanes = (size_t)blocks * BLOCK;
   uint32_t *pts, *out_a, *out_b, *scratch, *pb, *cb, *ab; uint8_t* k; unsigned* bad;
   CK(hipMalloc(&pts, n * 192)); CK(hipMalloc(&out_a, n * 192)); CK(hipMalloc(&out_b, n * 192)); CK(hipMalloc(&k, n * 32)); CK(hipMalloc(&bad, 4));
-  CK(hipMalloc(&scratch, lanes * VB_ENTRIES * VB_ENTRY_WORDS * 4));
+  CK(hipMalloc(&scratch, lanes * VB_ENTRIES * BM_ENTRY_WORDS * 4));
   CK(hipMalloc(&pb, lanes * CHUNK_E * 8 * 3 * SLOT * 4)); CK(hipMalloc(&cb, lanes * CHUNK_E * 8 * SLOT * 4)); CK(hipMalloc(&ab, lanes * CHUNK_E * 9 * AP_WORDS * 4));
   hipLaunchKernelGGL(k_fill, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, pts, n);
   std::vector<uint8_t> hk(n * 32); uint64_t s = 88172645463325252ull;
