@@ -891,6 +891,7 @@ D377_HD void fr_recode_signed16(const uint32_t k[8], uint32_t digits[8]) {
     digits[wi] = outw;
   }
   // k < 2^251 -> nibble 62 is <= 7 + carry, nibble 63 is the final carry (0 or 1): no overflow
+  // (a reduced scalar is tighter: k < r < 5 * 2^248 gives digit 62 in 0..5 and digit 63 = 0 -- ge_scalar_mul_w4_lean)
 }
 D377_HD int fr_digit(const uint32_t digits[8], int i) {   // signed value of nibble i
   uint32_t n = (digits[i >> 3] >> (4 * (i & 7))) & 15u;
@@ -961,6 +962,29 @@ D377_HD ge_of<F> ge_double_neg(const ge_of<F>& p, bool with_t) {
   F g = fe_sub(a, b);                     // carried
   F f = fe_add(g, c);                     // lazy
   ge_of<F> r;
+  r.x = fe_mul(e, f); r.y = fe_mul(g, h); r.z = fe_mul(f, g);
+  r.t = p.t;
+  if (with_t) r.t = fe_mul(e, h);
+  return r;
+}
+
+// -[2]P on signed limbs, with 2XY taken from a squaring: E = (A + B) - (X - Y)^2, true sign, the rest as ge_double_neg.
+// ge_double_neg's pricing of a squaring form (222 against 205) is the unsigned field's, where a difference costs an
+// offset and a carry pass.  On fes a difference is one instruction per limb and never carries, X - Y of two products (or
+// of two carried coordinates) has limbs inside +-2^29, which a squaring may double, and A + B is there already as H':
+// fe_sub + sqr + fe_sub = 9 + 159 + 9 = 177 instructions against fe_dbl + mul = 9 + 187 = 196, and 36 fewer MACs.
+// E's limbs lie in (-2^29, 2^30) and meet the lazy F' and H' in two products: the bounds build walks every column of both.
+// k_scalar_mul_var / k_scalar_mul_var_el run this one (ge_scalar_mul_w4_lean); ge_double_neg above stays the statement
+// of the quad, wave and Straus chains on fe, and the reference statement the host simulations of tests/host_sim walk.
+D377_HD ge_of<fes> ge_double_neg_sq(const ge_of<fes>& p, bool with_t) {
+  fes a = fe_sqr(p.x), b = fe_sqr(p.y);
+  fes c = fe_sqr2x(p.z);
+  fes s_ = fe_sqr(fe_sub(p.x, p.y));      // A + B - 2XY
+  fes h = fe_add(a, b);
+  fes e = fe_sub(h, s_);                  // 2XY
+  fes g = fe_sub(a, b);
+  fes f = fe_add(g, c);
+  ge_of<fes> r;
   r.x = fe_mul(e, f); r.y = fe_mul(g, h); r.z = fe_mul(f, g);
   r.t = p.t;
   if (with_t) r.t = fe_mul(e, h);
@@ -1089,6 +1113,56 @@ D377_HD ge ge_scalar_mul_w4(const ge& p0, const uint32_t digits[8], Tab& tab, bo
     const gec_of<F> e = tab.load(neg ? -d : d, neg);
 #pragma unroll 1
     for (int j = 0; j < 4; ++j) r = ge_double_neg(r, j == 3);   // (-2)^4 = 16
+    r = ge_add_cached(r, e, neg, want_t && i == 0);   // only the last T can have a reader
+  }
+  return ge_unsigned(r);
+}
+
+// The chain k_scalar_mul_var / k_scalar_mul_var_el run: the same table protocol, result and table contents as
+// ge_scalar_mul_w4<fes> above (which stays as the reference statement: tests/host_sim/sim.cpp and signed_sim.cpp walk it
+// and pin its product counts), less two pieces of work the result does not need.
+//  * The top window.  The scalar is reduced: k < r = 0x04aa.. * 2^240 < 5 * 2^248.  Nibble 63 of k is therefore 0 and
+//    nibble 62 at most 4; with the carry from below, digit 62 lies in 0..5, gives no carry, and digit 63 is 0.  So the
+//    chain above always starts from the identity, and its first trip doubles the identity four times and adds entry
+//    d62 to it: 12 S + 24 M for [d62]P, which the table holds already.  Here the start value is lifted from entry d62:
+//    (Y+X) - (Y-X), (Y+X) + (Y-X), 2Z are 2X, 2Y, 2Z, the same projective point (entry 0 gives 0 : 2 : 2, the identity),
+//    and the loop runs 62 windows.  T is not lifted: the window's doublings do not read it and the fourth writes it.
+//    One carry pass each brings the three coordinates back under what a squaring may double (a limb table holds y + x
+//    and 2z of a carried input with limbs up to 2^30 + 16).  Digit 63 is not read; the bounds build requires it to be 0.
+//    (Holding [d62]P back in registers while the table is built, by per-lane selects, was the first form: 27 more live
+//    VGPRs through the build, which took k_scalar_mul_var to 22 spilled VGPRs and k_scalar_mul_var_el to 8.)
+//  * 2XY from a squaring: ge_double_neg_sq.
+// Per element with the decompression and the compressor of k_scalar_mul_var: 1396.5 M + 1245 S (above: 1668.5 + 1009).
+// The result is the same group element; its projective representative differs from the chain above.
+template <class F = fes, class Tab>
+D377_HD ge ge_scalar_mul_w4_lean(const ge& p0, const uint32_t digits[8], Tab& tab, bool want_t = true) {
+  static_assert(std::is_same<F, fes>::value, "ge_double_neg_sq is priced and bounded for signed limbs");
+  const ge_of<F> p = ge_as<F>(p0);
+  if constexpr (!tab_shares_identity<Tab>::value) tab.store(0, gec_identity<F>());
+  const gec_of<F> pc = ge_to_cached(p);
+  tab.store(1, pc);
+  ge_of<F> acc = ge_double_fast(p, true);
+  tab.store(2, ge_to_cached(acc));
+#pragma unroll 1
+  for (int j = 3; j <= 8; ++j) {
+    acc = ge_add_cached(acc, pc, false, true);
+    tab.store(j, ge_to_cached(acc));
+  }
+  D377_B(bound_require(fr_digit(digits, 63) == 0 && fr_digit(digits, 62) >= 0 && fr_digit(digits, 62) <= 5,
+                       "lean window chain: the scalar is not below r"));
+  const int top = fr_digit(digits, 62) & 7;     // 0..5; the mask keeps the index inside the table whatever a caller passes
+  const gec_of<F> s = tab.load(top, false);
+  ge_of<F> r;
+  r.x = fe_carry(fe_sub(s.ypx, s.ymx)); r.y = fe_carry(fe_add(s.ypx, s.ymx)); r.z = fe_carry(s.z2);
+  r.t = fe_as<F>(fe_zero());                    // no reader
+#pragma unroll 1
+  for (int i = 61; i >= 0; --i) {
+    // fetch this window's table entry first, as above
+    const int d = fr_digit(digits, i);
+    const bool neg = d < 0;
+    const gec_of<F> e = tab.load(neg ? -d : d, neg);
+#pragma unroll 1
+    for (int j = 0; j < 4; ++j) r = ge_double_neg_sq(r, j == 3);   // (-2)^4 = 16
     r = ge_add_cached(r, e, neg, want_t && i == 0);   // only the last T can have a reader
   }
   return ge_unsigned(r);

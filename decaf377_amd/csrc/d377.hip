@@ -431,7 +431,7 @@ __global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD) k_scalar_mul_var(SqrtTa
       fr_reduce_words(k);
       fr_half_words(k);
       fr_recode_signed16(k, dg);
-      const ge r = ge_scalar_mul_w4<fes>(g, dg, tab, DCB_WANT_T);     // (r: back in fe, carried)
+      const ge r = ge_scalar_mul_w4_lean<fes>(g, dg, tab, DCB_WANT_T);   // 62 windows (curve.hpp); r: back in fe, carried
       D377_INVARIANT(T, r, bad == 0);
       dcb_put(io, j, ge_dcb_from_half(r, bad != 0));      // failed lanes: neutral state, all-zero output
     });
@@ -942,7 +942,7 @@ __global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD) k_scalar_mul_var_el(con
       const ge g = load_ge_mont256(xyzt, i);
       fr_reduce_words(k);
       fr_recode_signed16(k, dg);
-      store_ge_mont256(out, i, ge_scalar_mul_w4<fes>(g, dg, tab));
+      store_ge_mont256(out, i, ge_scalar_mul_w4_lean<fes>(g, dg, tab));
     }
   }
   dcb_release(dcb, slot);
