@@ -39,6 +39,7 @@
 #include "host_state.hpp"
 #include "codec_chunked.hpp"
 #include "batch_msm_long_plan.hpp"
+#include "msm_long_fold.hpp"
 
 using namespace d377;
 
@@ -241,6 +242,52 @@ int ensure_partials(DeviceState& d, size_t bytes) {
   return D377_OK;
 }
 
+}  // namespace
+
+// ---- what both this unit's chains and fixed_bases.hip's segments end in (msm_long_fold.hpp) ----------------------------------
+namespace d377 {
+
+int long_sums_partials(DeviceState& d, hipStream_t s, size_t n, size_t g, uint64_t** partials) {
+  *partials = nullptr;
+  if (partial_records(n, g) * 128 > d.bml_cap && ScratchGuard::capturing(s))
+    return fail(D377_ERR_ARG, "%s", "batch_msm_long: the partial sums' area must grow, which cannot happen inside a stream capture");
+  int rc;
+  if ((rc = ensure_partials(d, partial_records(n, g) * 128))) return rc;
+  *partials = reinterpret_cast<uint64_t*>(d.bml_partials);
+  return D377_OK;
+}
+
+int long_sums_fold_compress(DeviceState& d, hipStream_t s, size_t n, size_t g, uint8_t* out32, uint64_t* xyzt_out) {
+  uint64_t* partials = reinterpret_cast<uint64_t*>(d.bml_partials);
+  const size_t np = n * g;
+  uint64_t* half[2] = {partials + np * 16, partials + (np + n * fold_out(g)) * 16};
+
+  // ---- fold levels until one record per sum is left; the last level writes the caller's Element records if asked
+  const uint64_t* cur = partials;
+  int turn = 0;
+  for (size_t c = g; c > 1; c = fold_out(c)) {
+    const size_t oc = fold_out(c), lanes = n * oc;
+    uint64_t* dst = (oc == 1 && xyzt_out) ? xyzt_out : half[turn];
+    size_t grid = (lanes + BLOCK - 1) / BLOCK;
+    if (grid > (size_t)d.cus * 8) grid = (size_t)d.cus * 8;
+    hipLaunchKernelGGL(k_msm_long_fold, dim3((unsigned)grid), dim3(BLOCK), 0, s, cur, c, n, dst);
+    HIP_TRY(hipGetLastError());
+    cur = dst;
+    turn ^= 1;
+  }
+
+  // ---- the sums' Encodings, in chunks with batched inversions (codec_chunked.hip); the chunks as batch_msm_launch deals them
+  const size_t places = (size_t)d.cus * WAVES_PER_SIMD;
+  const ChunkDeal c = deal_chunks((n + BLOCK - 1) / BLOCK, places, (size_t)DCB_K, (size_t)d.cus * 64);
+  DcbScratch dcb{d.dcb_scratch, d.slot_pool, d.cus * WAVES_PER_SIMD, (int)c.per_lane, d.dcb_sets * BLOCK, (int)c.extra, d.pool_health};
+  dcb.prio = c.nchunks <= 2 * places ? 1 : 0;
+  return codec_chunked_launch(d, s, false, cur, n, out32, nullptr, (int)c.nchunks, dcb);
+}
+
+}  // namespace d377
+
+namespace {
+
 // everything on device pointers, enqueued on `s`; the caller holds ctx->mu.  m > 8.
 int batch_msm_long_launch(DeviceState& d, hipStream_t s, bool encoded, const void* pts_in, const uint8_t* scalars, size_t m, size_t n,
                           uint8_t* out32, uint64_t* xyzt_out, uint8_t* status) {
@@ -252,11 +299,8 @@ int batch_msm_long_launch(DeviceState& d, hipStream_t s, bool encoded, const voi
     return fail(D377_ERR_INIT, "residency of %s does not match the lane sets of the scratch areas", "k_compress_chunked");
   GuardScope vb{d.vb_guard, s};                              // the lane-set areas, the table scratch, the partials: queue behind their last user
   int rc;
-  if (partial_records(n, plan.g) * 128 > d.bml_cap && ScratchGuard::capturing(s))
-    return fail(D377_ERR_ARG, "%s", "batch_msm_long: the partial sums' area must grow, which cannot happen inside a stream capture");
-  if ((rc = ensure_partials(d, partial_records(n, plan.g) * 128))) return rc;
-  uint64_t* partials = reinterpret_cast<uint64_t*>(d.bml_partials);
-  uint64_t* half[2] = {partials + np * 16, partials + (np + n * fold_out(plan.g)) * 16};
+  uint64_t* partials = nullptr;
+  if ((rc = long_sums_partials(d, s, n, plan.g, &partials))) return rc;
   const size_t places = (size_t)d.cus * WAVES_PER_SIMD;
   auto deal = [&](size_t count, int& grid) {                 // the chunks of a lane-set kernel over `count` elements (as batch_msm_launch)
     const ChunkDeal c = deal_chunks((count + BLOCK - 1) / BLOCK, places, (size_t)DCB_K, (size_t)d.cus * 64);
@@ -317,24 +361,8 @@ int batch_msm_long_launch(DeviceState& d, hipStream_t s, bool encoded, const voi
     HIP_TRY(hipGetLastError());
   }
 
-  // ---- phase 2: fold levels until one record per sum is left; the last level writes the caller's Element records if asked
-  const uint64_t* cur = partials;
-  int turn = 0;
-  for (size_t c = plan.g; c > 1; c = fold_out(c)) {
-    const size_t oc = fold_out(c), lanes = n * oc;
-    uint64_t* dst = (oc == 1 && xyzt_out) ? xyzt_out : half[turn];
-    size_t grid = (lanes + BLOCK - 1) / BLOCK;
-    if (grid > (size_t)d.cus * 8) grid = (size_t)d.cus * 8;
-    hipLaunchKernelGGL(k_msm_long_fold, dim3((unsigned)grid), dim3(BLOCK), 0, s, cur, c, n, dst);
-    HIP_TRY(hipGetLastError());
-    cur = dst;
-    turn ^= 1;
-  }
-
-  // ---- phase 3: the sums' Encodings, in chunks with batched inversions (codec_chunked.hip)
-  int grid = 0;
-  const DcbScratch dcb = deal(n, grid);
-  if ((rc = codec_chunked_launch(d, s, false, cur, n, out32, nullptr, grid, dcb))) return rc;
+  // ---- phases 2 and 3: the fold levels, then the sums' Encodings (msm_long_fold.hpp)
+  if ((rc = long_sums_fold_compress(d, s, n, plan.g, out32, xyzt_out))) return rc;
   return vb.finish();
 }
 

@@ -4,6 +4,10 @@
 //   d377_batch_fixed_msm      out[i] = sum_j scalar[i m + j] * B_j, one lane per sum
 //   d377_batch_fixed_msm_indexed   out[i] = sum_{j < t} scalar[i t + j] * B_{base_index[i t + j]}: the same walk, each term in
 //                             the comb it names (curve.hpp: ge_fixed_msm_indexed_w8); -1 = the term is absent
+//   d377_fixed_bases_create_long   the same registration for up to D377_FIXED_BASES_LONG_MAX = 4096 bases
+//   d377_batch_fixed_long_msm      the dense sums with every sum cut into g segments of consecutive bases
+//                             (fixed_msm_long_plan.hpp), one lane per segment (k_fixed_msm_seg); the segments' partial sums are
+//                             folded and compressed as d377_batch_msm_long's are (msm_long_fold.hpp).  g = 1: the kernel above
 //
 // The sum is k_scalar_mul_base's walk widened to m combs (curve.hpp: ge_fixed_msm_w8): each base's scalar is reduced and
 // halved, its W signed digits pick one entry per window, and all m x W mixed additions go into ONE accumulator -- no
@@ -32,12 +36,17 @@
 #include "dcb.hpp"
 #include "host_state.hpp"
 #include "fixed_comb.hpp"
+#include "codec_chunked.hpp"
+#include "fixed_msm_long_plan.hpp"
+#include "msm_long_fold.hpp"
 
 using namespace d377;
 
 namespace {
 
 constexpr int FX_MAX = D377_FIXED_BASES_MAX;
+constexpr int FX_LONG_MAX = D377_FIXED_BASES_LONG_MAX;
+static_assert(FX_LONG_MAX <= 4096, "g <= m segments must fold in three levels of BML_FOLD = 16");
 
 // the m combs of a handle, back to back: entry c of window i of base j
 template <int BITS>
@@ -110,6 +119,42 @@ k_fixed_msm_indexed_lane(SqrtTables T, const uint32_t* tabs, const int* base_ind
   D377_DCB_END();
 }
 
+// The dense sum cut into segments (fixed_msm_long_plan.hpp): one lane per PARTIAL sum, a plain grid-stride kernel.  No table
+// scratch and no inversion, so it claims no lane set and cannot starve.  Lane P takes segment q = P / n of sum s = P % n --
+// segment-major, so the lanes of a wave gather from the SAME combs and few combs are in flight chip-wide at any moment -- and
+// writes record s g + q, sum-major, because the fold adds consecutive records of a sum.  The record is the double of the
+// walk's result (the walk ran on k / 2), what k_msm_long_lane writes.  (-DD377_FML_SUM_MAJOR: the A/B build with sum-major lanes.)
+template <class FTab>
+struct FbOffsetTabs {
+  const FTab& tabs;
+  int first;                                                       // the segment's first base
+  __device__ __forceinline__ gea load(int j, int i, int c, bool swap) const { return tabs.load(first + j, i, c, swap); }
+};
+template <int BITS>
+__global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD)
+k_fixed_msm_seg(SqrtTables T, const uint32_t* tabs, const uint8_t* scalar32, FixedLongPlan plan, size_t n, uint64_t* partials) {
+  const CombTabs<BITS> ft{tabs};
+  const size_t total = n * plan.g;
+#pragma unroll 1
+  for (size_t P = (size_t)blockIdx.x * BLOCK + threadIdx.x; P < total; P += (size_t)gridDim.x * BLOCK) {
+#ifdef D377_FML_SUM_MAJOR
+    const size_t s = P / plan.g, q = P % plan.g;
+#else
+    const size_t q = P / n, s = P % n;
+#endif
+    const size_t first = s * plan.m + plan.first(q);
+    const FbOffsetTabs<CombTabs<BITS>> st{ft, (int)plan.first(q)};
+    const ge r = ge_fixed_msm_w8<BITS>((int)plan.count(q), [&](int p, uint32_t k[8]) {
+      load32(scalar32, first + (size_t)p, k);
+      fr_reduce_words(k);
+      fr_half_words(k);
+    }, st, /*want_t=*/false);
+    const ge sum = ge_double_fast(r, true);
+    D377_INVARIANT(T, sum, true);
+    store_ge_mont256(partials, s * plan.g + q, sum);
+  }
+}
+
 // ------------------------------------------------------------------------------ host side ---
 // The comb widths a handle may ask for; f(std::integral_constant<int, BITS>) runs with the kernels of that width.
 int width_slot(int bits) { return bits == 8 ? 0 : bits == 12 ? 1 : bits == 16 ? 2 : bits == 18 ? 3 : -1; }
@@ -158,7 +203,7 @@ int check_residency_of(const void* fn, const char* name, int bits, int& lds) {
 // the combs of `m` bases on one device: residency check, allocation, window bases, one build launch, synchronised.
 // On failure nothing of this device is left allocated.  Caller holds ctx->mu.
 template <int BITS>
-int build_on(DeviceState& d, const uint64_t* xyzt, size_t m, uint32_t** out) {
+int build_on(DeviceState& d, const char* who, const uint64_t* xyzt, size_t m, uint32_t** out) {
   using Sh = FbShape<BITS>;
   *out = nullptr;
   HIP_TRY(hipSetDevice(d.id));
@@ -173,14 +218,14 @@ int build_on(DeviceState& d, const uint64_t* xyzt, size_t m, uint32_t** out) {
     (void)hipGetLastError();
     tab = nullptr;
     snprintf(d377_g_err, sizeof d377_g_err,
-             "d377_fixed_bases_create: the combs need %.3f GB of device memory and the allocation failed (device %d): fewer bases or a "
-             "narrower comb_bits", (double)bytes / 1e9, d.id);
+             "%s: the combs need %.3f GB of device memory and the allocation failed (device %d): fewer bases or a "
+             "narrower comb_bits", who, (double)bytes / 1e9, d.id);
     return D377_ERR_HIP;
   }
   if (hipMalloc(&rec, m * 16 * sizeof(uint64_t)) != hipSuccess || hipMalloc(&wb, nwin * 4 * SLOT * sizeof(uint32_t)) != hipSuccess) {
     (void)hipGetLastError();
     cleanup();
-    return fail(D377_ERR_HIP, "%s", "d377_fixed_bases_create: hipMalloc failed (window bases)");
+    return fail(D377_ERR_HIP, "%s: hipMalloc failed (window bases)", who);
   }
   hipError_t e = hipMemcpyAsync(rec, xyzt, m * 16 * sizeof(uint64_t), hipMemcpyHostToDevice, d.stream);
   if (e == hipSuccess) {
@@ -194,7 +239,8 @@ int build_on(DeviceState& d, const uint64_t* xyzt, size_t m, uint32_t** out) {
   (void)hipFree(wb); wb = nullptr;
   if (e != hipSuccess) {
     cleanup();
-    return fail(D377_ERR_HIP, "d377_fixed_bases_create: building the combs: %s", hipGetErrorString(e));
+    snprintf(d377_g_err, sizeof d377_g_err, "%s: building the combs: %s", who, hipGetErrorString(e));
+    return D377_ERR_HIP;
   }
   *out = tab;
   return D377_OK;
@@ -227,9 +273,37 @@ int fixed_msm_launch(DeviceState& d, hipStream_t s, const FixedBases& fb, const 
   return vb.finish();
 }
 
+// the cut of n dense sums on device d (n >= 1)
+FixedLongPlan cut_of(const DeviceState& d, const FixedBases& fb, size_t n) { return fixed_long_plan(fb.m, n, d.resident_lanes()); }
+
+// The dense sums cut into segments; everything on device pointers, enqueued on `s`; the caller holds ctx->mu.  One segment per
+// sum is fixed_msm_launch, the same bytes.
+int fixed_msm_long_launch(DeviceState& d, hipStream_t s, const FixedBases& fb, const uint32_t* tab, const uint8_t* scalars, size_t n,
+                          uint8_t* out32, uint64_t* xyzt_out) {
+  if (n == 0) return D377_OK;
+  const FixedLongPlan plan = cut_of(d, fb, n);
+  if (plan.g == 1) return fixed_msm_launch(d, s, fb, tab, nullptr, fb.m, scalars, n, out32, xyzt_out);
+  if (!codec_chunked_ok(d))
+    return fail(D377_ERR_INIT, "residency of %s does not match the lane sets of the scratch areas", "k_compress_chunked");
+  GuardScope vb{d.vb_guard, s};                              // the partials and, for the compressor, the lane-set areas
+  int rc;
+  uint64_t* partials = nullptr;
+  if ((rc = long_sums_partials(d, s, n, plan.g, &partials))) return rc;
+  if ((rc = vb.acquire())) return rc;
+  size_t grid = (n * plan.g + BLOCK - 1) / BLOCK;
+  if (grid > (size_t)d.cus * 8) grid = (size_t)d.cus * 8;    // (as the fold's)
+  const SqrtTables T = d.tables();
+  if ((rc = with_width(fb.bits, [&](auto b) -> int {
+         hipLaunchKernelGGL(k_fixed_msm_seg<decltype(b)::value>, dim3((unsigned)grid), dim3(BLOCK), 0, s, T, tab, scalars, plan, n, partials);
+         return D377_OK; }))) return rc;
+  HIP_TRY(hipGetLastError());
+  if ((rc = long_sums_fold_compress(d, s, n, plan.g, out32, xyzt_out))) return rc;
+  return vb.finish();
+}
+
 // one device's slice of a host batch: copies in, kernel, copies out, synchronised.  index == null: dense, t = m; otherwise the
-// slice's n x t indices, staged behind its scalars (n t x 32 bytes: 16-byte aligned).
-int fixed_msm_one(DeviceState& d, const FixedBases& fb, const uint32_t* tab, const int* index, size_t t, const uint8_t* scalars,
+// slice's n x t indices, staged behind its scalars (n t x 32 bytes: 16-byte aligned).  cut: the dense sums in segments.
+int fixed_msm_one(DeviceState& d, const FixedBases& fb, const uint32_t* tab, const int* index, size_t t, bool cut, const uint8_t* scalars,
                   size_t n, uint8_t* out32, uint64_t* xyzt_out) {
   if (n == 0) return D377_OK;
   HIP_TRY(hipSetDevice(d.id));
@@ -246,7 +320,9 @@ int fixed_msm_one(DeviceState& d, const FixedBases& fb, const uint32_t* tab, con
     const int* index_dev = index ? reinterpret_cast<const int*>(d.buf[1] + terms * 32) : nullptr;
     if (index) HIP_TRY(hipMemcpyAsync(d.buf[1] + terms * 32, index, terms * sizeof(int), hipMemcpyHostToDevice, d.stream));
     uint64_t* xyzt_dev = xyzt_out ? reinterpret_cast<uint64_t*>(d.buf[2] + n * 32) : nullptr;
-    if ((r = fixed_msm_launch(d, d.stream, fb, tab, index_dev, t, d.buf[1], n, d.buf[2], xyzt_dev))) return r;
+    if (cut) r = fixed_msm_long_launch(d, d.stream, fb, tab, d.buf[1], n, d.buf[2], xyzt_dev);
+    else r = fixed_msm_launch(d, d.stream, fb, tab, index_dev, t, d.buf[1], n, d.buf[2], xyzt_dev);
+    if (r) return r;
     HIP_TRY(hipMemcpyAsync(out32, d.buf[2], n * 32, hipMemcpyDeviceToHost, d.stream));
     if (xyzt_out) HIP_TRY(hipMemcpyAsync(xyzt_out, xyzt_dev, n * 128, hipMemcpyDeviceToHost, d.stream));
     if ((r = starve.after())) return r;
@@ -258,12 +334,12 @@ int fixed_msm_one(DeviceState& d, const FixedBases& fb, const uint32_t* tab, con
 }
 
 // n sums in contiguous slices over the context's devices, one host thread per device (as batch_msm.hip); t terms per sum,
-// index == null for the dense sums.  Caller holds ctx->mu.
-int fixed_msm_sliced(d377_ctx* ctx, const FixedBases& fb, const int* index, size_t t, const uint8_t* scalar32, size_t n,
+// index == null for the dense sums, which `cut` has every device cut into segments.  Caller holds ctx->mu.
+int fixed_msm_sliced(d377_ctx* ctx, const FixedBases& fb, const int* index, size_t t, bool cut, const uint8_t* scalar32, size_t n,
                      uint8_t* enc32_out, uint64_t* xyzt_out) {
   if (n == 0) return D377_OK;
   const size_t nd = ctx->devs.size();
-  if (nd == 1) return fixed_msm_one(ctx->devs[0], fb, fb.tab[0], index, t, scalar32, n, enc32_out, xyzt_out);
+  if (nd == 1) return fixed_msm_one(ctx->devs[0], fb, fb.tab[0], index, t, cut, scalar32, n, enc32_out, xyzt_out);
   const size_t per = (n + nd - 1) / nd;
   std::vector<int> rcs(nd, D377_OK);
   std::vector<std::string> errs(nd);
@@ -275,7 +351,7 @@ int fixed_msm_sliced(d377_ctx* ctx, const FixedBases& fb, const int* index, size
     const size_t cnt = (lo + per <= n) ? per : n - lo;
     workers.emplace_back([&, k, lo, cnt]() {
       if (delay > 0) std::this_thread::sleep_for(std::chrono::milliseconds(delay));
-      rcs[k] = fixed_msm_one(ctx->devs[k], fb, fb.tab[k], index ? index + lo * t : nullptr, t, scalar32 + lo * t * 32, cnt,
+      rcs[k] = fixed_msm_one(ctx->devs[k], fb, fb.tab[k], index ? index + lo * t : nullptr, t, cut, scalar32 + lo * t * 32, cnt,
                              enc32_out + lo * 32, xyzt_out ? xyzt_out + lo * 16 : nullptr);
       if (rcs[k] != D377_OK) errs[k] = d377_g_err;
     });
@@ -306,6 +382,37 @@ FixedBases* find(d377_ctx* ctx, int64_t handle) {
   return nullptr;
 }
 
+// the registration itself, arguments checked: the combs on every device, then the handle.  On failure nothing is left allocated.
+int register_bases(d377_ctx* ctx, const char* who, const uint64_t* xyzt, size_t m, int bits, int64_t* handle_out) {
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  FixedBases* fb = new (std::nothrow) FixedBases;
+  if (!fb) return fail(D377_ERR_ARG, "%s: out of host memory", who);
+  fb->m = m;
+  fb->bits = bits;
+  fb->tab.assign(ctx->devs.size(), nullptr);
+  int rc = with_width(bits, [&](auto b) -> int {
+    constexpr int BITS = decltype(b)::value;
+    fb->bytes = (uint64_t)(m * comb_bytes<BITS>());
+    for (size_t k = 0; k < ctx->devs.size(); ++k) {
+      const int r = build_on<BITS>(ctx->devs[k], who, xyzt, m, &fb->tab[k]);
+      if (r) return r;
+    }
+    return D377_OK;
+  });
+  if (rc) {
+    char saved[sizeof d377_g_err];
+    memcpy(saved, d377_g_err, sizeof saved);
+    free_tables(ctx, fb);
+    delete fb;
+    memcpy(d377_g_err, saved, sizeof saved);
+    return rc;
+  }
+  fb->handle = ctx->next_fixed++;
+  ctx->fixed.push_back(fb);
+  *handle_out = fb->handle;
+  return D377_OK;
+}
+
 }  // namespace
 
 namespace d377 {
@@ -329,33 +436,20 @@ int d377_fixed_bases_create(d377_ctx* ctx, const uint64_t* xyzt, size_t m, int c
   if (!xyzt) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create: xyzt is null");
   if (!handle_out) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create: handle_out is null");
   if (!ctx) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create: ctx is null");
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  FixedBases* fb = new (std::nothrow) FixedBases;
-  if (!fb) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create: out of host memory");
-  fb->m = m;
-  fb->bits = bits;
-  fb->tab.assign(ctx->devs.size(), nullptr);
-  int rc = with_width(bits, [&](auto b) -> int {
-    constexpr int BITS = decltype(b)::value;
-    fb->bytes = (uint64_t)(m * comb_bytes<BITS>());
-    for (size_t k = 0; k < ctx->devs.size(); ++k) {
-      const int r = build_on<BITS>(ctx->devs[k], xyzt, m, &fb->tab[k]);
-      if (r) return r;
-    }
-    return D377_OK;
-  });
-  if (rc) {
-    char saved[sizeof d377_g_err];
-    memcpy(saved, d377_g_err, sizeof saved);
-    free_tables(ctx, fb);
-    delete fb;
-    memcpy(d377_g_err, saved, sizeof saved);
-    return rc;
-  }
-  fb->handle = ctx->next_fixed++;
-  ctx->fixed.push_back(fb);
-  *handle_out = fb->handle;
-  return D377_OK;
+  return register_bases(ctx, "d377_fixed_bases_create", xyzt, m, bits, handle_out);
+}
+
+// the same registration with room for 4096 bases; nothing in the comb layout depends on the count (fixed_comb.hpp)
+int d377_fixed_bases_create_long(d377_ctx* ctx, const uint64_t* xyzt, size_t m, int comb_bits, int64_t* handle_out) {
+  if (handle_out) *handle_out = 0;
+  if (m < 1 || m > (size_t)FX_LONG_MAX)
+    return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create_long: m must be 1 .. 4096 bases (D377_FIXED_BASES_LONG_MAX)");
+  const int bits = comb_bits == 0 ? 12 : comb_bits;
+  if (width_slot(bits) < 0) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create_long: comb_bits must be 8, 12, 16 or 18 (0 = 12)");
+  if (!xyzt) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create_long: xyzt is null");
+  if (!handle_out) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create_long: handle_out is null");
+  if (!ctx) return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create_long: ctx is null");
+  return register_bases(ctx, "d377_fixed_bases_create_long", xyzt, m, bits, handle_out);
 }
 
 int d377_fixed_bases_info(d377_ctx* ctx, int64_t handle, uint64_t* m, int* comb_bits, uint64_t* table_bytes_per_device) {
@@ -387,7 +481,8 @@ int d377_batch_fixed_msm(d377_ctx* ctx, int64_t handle, const uint8_t* scalar32,
   std::lock_guard<std::mutex> lock(ctx->mu);
   const FixedBases* fb = find(ctx, handle);
   if (!fb) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_msm: handle is not a live registration of this context");
-  return fixed_msm_sliced(ctx, *fb, nullptr, fb->m, scalar32, n, enc32_out, xyzt_out);
+  // more bases than d377_fixed_bases_create registers: the same sum, cut into segments (d377_batch_fixed_long_msm)
+  return fixed_msm_sliced(ctx, *fb, nullptr, fb->m, fb->m > (size_t)FX_MAX, scalar32, n, enc32_out, xyzt_out);
 }
 
 // the same slices; the index rows and scalar rows of a sum travel with it
@@ -415,7 +510,36 @@ int d377_batch_fixed_msm_indexed(d377_ctx* ctx, int64_t handle, const int* base_
       return D377_ERR_ARG;
     }
   }
-  return fixed_msm_sliced(ctx, *fb, base_index, t, scalar32, n, enc32_out, xyzt_out);
+  return fixed_msm_sliced(ctx, *fb, base_index, t, false, scalar32, n, enc32_out, xyzt_out);
+}
+
+// the dense sums, every sum cut into segments where that fills the chip; any live handle
+int d377_batch_fixed_long_msm(d377_ctx* ctx, int64_t handle, const uint8_t* scalar32, size_t n, uint8_t* enc32_out, uint64_t* xyzt_out) {
+  if (!ctx) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_long_msm: ctx is null");
+  if (n && (!scalar32 || !enc32_out)) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_long_msm: null buffer");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  const FixedBases* fb = find(ctx, handle);
+  if (!fb) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_long_msm: handle is not a live registration of this context");
+  return fixed_msm_sliced(ctx, *fb, nullptr, fb->m, true, scalar32, n, enc32_out, xyzt_out);
+}
+
+// how device `dev` of the context cuts its slice of a call of n sums (fixed_msm_sliced: ceil(n / devices) sums per device)
+int d377_fixed_long_msm_plan(d377_ctx* ctx, int64_t handle, size_t n, int dev, uint64_t* segments, uint64_t* bases_per_segment) {
+  if (segments) *segments = 0;
+  if (bases_per_segment) *bases_per_segment = 0;
+  if (!ctx) return fail(D377_ERR_ARG, "%s", "d377_fixed_long_msm_plan: ctx is null");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  const FixedBases* fb = find(ctx, handle);
+  if (!fb) return fail(D377_ERR_ARG, "%s", "d377_fixed_long_msm_plan: handle is not a live registration of this context");
+  const size_t nd = ctx->devs.size();
+  if (dev < 0 || (size_t)dev >= nd) return fail(D377_ERR_ARG, "%s", "d377_fixed_long_msm_plan: dev is not a device of this context");
+  const size_t per = (n + nd - 1) / nd, lo = per * (size_t)dev;
+  const size_t cnt = lo >= n ? 0 : (lo + per <= n ? per : n - lo);
+  if (cnt == 0) return D377_OK;                               // no sums for this device: 0 segments
+  const FixedLongPlan plan = cut_of(ctx->devs[(size_t)dev], *fb, cnt);
+  if (segments) *segments = plan.g;
+  if (bases_per_segment) *bases_per_segment = plan.b;
+  return D377_OK;
 }
 
 }  // extern "C"

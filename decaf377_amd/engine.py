@@ -178,6 +178,12 @@ class Context:
         Returns a FixedBases; it keeps this context alive and is closed before it."""
         return FixedBases(points, comb_bits=comb_bits, ctx=self)
 
+    def fixed_bases_long(self, points, comb_bits=12):
+        """Registers 1 <= m <= 4096 fixed bases (d377_fixed_bases_create_long): fixed_bases with room for the generators of a
+        vector commitment -- 4096 bases are 2.2 GB at 8 bits and 22.5 GB at 12 on every device.  The FixedBases' msm cuts every
+        sum into segments that fill the chip (FixedBases.msm_long, which also takes a short registration)."""
+        return FixedBases(points, comb_bits=comb_bits, ctx=self, long=True)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             for fb in list(getattr(self, "_fixed", ())):          # handles first: d377_fixed_bases_destroy before d377_ctx_destroy
@@ -633,9 +639,10 @@ class FixedBases:
 
     points: an Element batch or an [m, 16] u64 array of Element records (numpy or torch; read once, at creation).
     comb_bits: 8, 12, 16 or 18.  ctx: the Context (default_context() if None); the FixedBases keeps it alive, and
-    Context.close() closes every FixedBases of the context first.  Usable as a context manager."""
+    Context.close() closes every FixedBases of the context first.  Usable as a context manager.
+    long: register with d377_fixed_bases_create_long, up to 4096 bases instead of 64 (Context.fixed_bases_long)."""
 
-    def __init__(self, points, comb_bits=16, ctx=None):
+    def __init__(self, points, comb_bits=16, ctx=None, long=False):
         if isinstance(points, Element):
             ctx = ctx or points.ctx
             points = points.data
@@ -650,8 +657,8 @@ class FixedBases:
         if not self.ctx._h:
             raise _native.NativeError("FixedBases: the context is closed")
         h = ctypes.c_int64(0)
-        _native.check(self._lib.d377_fixed_bases_create(self.ctx._h, pts.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(pts.shape[0]),
-                                                        int(comb_bits), ctypes.byref(h)))
+        create = self._lib.d377_fixed_bases_create_long if long else self._lib.d377_fixed_bases_create
+        _native.check(create(self.ctx._h, pts.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(pts.shape[0]), int(comb_bits), ctypes.byref(h)))
         self._h = int(h.value)
         if not hasattr(self.ctx, "_fixed"):
             import weakref
@@ -674,18 +681,34 @@ class FixedBases:
         """n sums over the registered bases: scalar32 [n * m, 32] u8, term-major within a sum (any 32 bytes, reduced mod r)
         -> enc [n, 32] u8, or (enc, xyzt [n, 16]) with elements=True.  A torch tensor is STAGED through host memory (the
         library has no device-pointer form of this call) and the results come back on its device."""
+        return self._dense("d377_batch_fixed_msm", "FixedBases.msm", scalar32, elements)
+
+    def msm_long(self, scalar32, elements=False):
+        """msm with every sum cut into segments of consecutive bases, one GPU lane per segment, where that fills the chip
+        (d377_batch_fixed_long_msm; long_plan shows the cut): few sums over many bases.  The same arguments and results as
+        msm, on a short or a long registration; msm on more than 64 bases is this call."""
+        return self._dense("d377_batch_fixed_long_msm", "FixedBases.msm_long", scalar32, elements)
+
+    def long_plan(self, n, dev=0):
+        """(segments per sum, bases per segment) of msm_long for the slice of n sums that device `dev` of the context gets:
+        d377_fixed_long_msm_plan."""
+        g, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _native.check(self._lib.d377_fixed_long_msm_plan(self.ctx._h, self._live(), ctypes.c_size_t(n), int(dev), ctypes.byref(g), ctypes.byref(b)))
+        return int(g.value), int(b.value)
+
+    def _dense(self, symbol, what, scalar32, elements):
         h = self._live()
         tdev = scalar32.device if _is_torch(scalar32) else None
         sc = np.ascontiguousarray(scalar32.detach().cpu().numpy() if tdev is not None else scalar32)
         terms = _rows(sc)
         if terms % self.m:
-            raise ValueError("FixedBases.msm: the number of scalars must be a multiple of m = %d" % self.m)
+            raise ValueError("%s: the number of scalars must be a multiple of m = %d" % (what, self.m))
         n = terms // self.m
-        _check(sc, ENC, terms, "FixedBases.msm scalars")
+        _check(sc, ENC, terms, what + " scalars")
         enc = np.empty((n, 32), np.uint8)
         xyzt = np.empty((n, 16), np.uint64) if elements else None
         p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        _native.check(self._lib.d377_batch_fixed_msm(self.ctx._h, h, p(sc), ctypes.c_size_t(n), p(enc), p(xyzt) if elements else None))
+        _native.check(getattr(self._lib, symbol)(self.ctx._h, h, p(sc), ctypes.c_size_t(n), p(enc), p(xyzt) if elements else None))
         if tdev is not None:
             import torch
             enc = torch.from_numpy(enc).to(tdev)

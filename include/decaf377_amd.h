@@ -371,8 +371,36 @@ int d377_batch_msm_long_encoded(d377_ctx* ctx, const uint8_t* enc32, const uint8
  * refused with D377_ERR_ARG.  Threads and lifetime: calls on one handle, or on several handles of one context, may come
  * from several host threads; they are serialised by the context's mutex like every host-pointer call.  Handles are
  * destroyed before their context; d377_ctx_destroy releases the tables of any handle still alive.  The C++ and Python
- * wrappers keep that order themselves.  d377_fixed_bases_info reports m, the comb width and the table bytes per device. */
+ * wrappers keep that order themselves.  d377_fixed_bases_info reports m, the comb width and the table bytes per device.
+ *
+ * Long registrations and long sums -- Pedersen vector commitments over hundreds or thousands of generators, the rounds of an
+ * inner-product argument, a value commitment that names its asset generator among thousands.
+ * d377_fixed_bases_create_long is d377_fixed_bases_create with 1 <= m <= D377_FIXED_BASES_LONG_MAX = 4096 bases and
+ * comb_bits 0 = 12: the same records (Z = 0 is the identity), the same build, handles of the same registry (d377_fixed_bases_info
+ * / _destroy, release with the context), the same checks in the same order -- m, comb_bits, xyzt, handle_out, ctx, all before
+ * any device is touched.  4096 bases are 2.2 GB at 8 bits and 22.5 GB at 12; tables that do not fit fail with D377_ERR_HIP,
+ * the message names the gigabytes, and nothing stays allocated.  d377_fixed_bases_create keeps its limit of 64.
+ *
+ * d377_batch_fixed_long_msm computes the sums of d377_batch_fixed_msm -- the same semantics, scalar reduction, argument checks
+ * and slicing of the SUMS over the devices -- on ANY live handle, short or long, with every sum cut into g segments of
+ * b consecutive bases, one GPU lane per segment: where d377_batch_fixed_msm gives a sum one lane (a thousand sums of 256 bases
+ * are a thousand lanes of a chip that holds 131 072), the cut fills the chip.  With L the device's resident lanes,
+ *     g0 = min(m, ceil(L / n)),  b = ceil(m / g0),  g = ceil(m / b)
+ * (b one less where rounding it up would leave the chip short by more than one segment per sum); the segments' partial sums
+ * are folded on the device, 16 records per lane and level, and compressed in one pass, as d377_batch_msm_long's are.
+ * n >= L or m = 1 is one segment per sum: d377_batch_fixed_msm's kernel and bytes.  d377_fixed_long_msm_plan reports g
+ * (`segments`) and b (`bases_per_segment`) for the slice device `dev` of the context gets of a call of n sums (0 and 0 where it
+ * gets none); it is pure and cheap and takes the context's mutex.  d377_batch_fixed_msm on a handle of more than 64 bases IS
+ * d377_batch_fixed_long_msm.  d377_batch_fixed_msm_indexed takes long handles as they are: indices 0 .. m-1 or -1, t <= 64.
+ * Against d377_batch_msm_long on the same sums (the m points replicated n times: 160 bytes uploaded per term instead of 32, a
+ * window table per copy, 252 doublings per chain and 64 additions per term) a term is 21 mixed additions at 12 bits and
+ * nothing else.  Measured (profiles/fixed_msm_long_bench.json, tools/bench_fixed_msm_long.py; host path): 2^12 sums of 256
+ * bases at 12 bits 2.23 ms against 10.61 ms, 2^8 sums of 4096 bases 2.32 ms against 10.67 ms (12 bits, 22.5 GB of combs) and
+ * 2.99 against 10.81 (8 bits), 2^16 sums of 65 bases 8.08 against 43.10; the kernel walks 1.70e10 additions per second over
+ * 22.5 GB of combs as over 2.2 GB.  256 sums over a 64-base handle: 0.39 ms against 3.64 ms through d377_batch_fixed_msm.
+ * For ONE sum use d377_msm: 0.45 ms against 0.60 ms at 4096 terms.  Host pointers only. */
 #define D377_FIXED_BASES_MAX 64
+#define D377_FIXED_BASES_LONG_MAX 4096
 int d377_fixed_bases_create(d377_ctx* ctx, const uint64_t* xyzt, size_t m, int comb_bits, int64_t* handle_out);
 int d377_fixed_bases_info(d377_ctx* ctx, int64_t handle, uint64_t* m, int* comb_bits, uint64_t* table_bytes_per_device);
 int d377_fixed_bases_destroy(d377_ctx* ctx, int64_t handle);
@@ -380,6 +408,11 @@ int d377_batch_fixed_msm(d377_ctx* ctx, int64_t handle, const uint8_t* scalar32,
                          uint64_t* xyzt_out);
 int d377_batch_fixed_msm_indexed(d377_ctx* ctx, int64_t handle, const int* base_index, const uint8_t* scalar32, size_t t,
                                  size_t n, uint8_t* enc32_out, uint64_t* xyzt_out);
+int d377_fixed_bases_create_long(d377_ctx* ctx, const uint64_t* xyzt, size_t m, int comb_bits, int64_t* handle_out);
+int d377_batch_fixed_long_msm(d377_ctx* ctx, int64_t handle, const uint8_t* scalar32, size_t n, uint8_t* enc32_out,
+                              uint64_t* xyzt_out);
+int d377_fixed_long_msm_plan(d377_ctx* ctx, int64_t handle, size_t n, int dev, uint64_t* segments,
+                             uint64_t* bases_per_segment);
 
 /* Fq field operations on in-memory elements (4 Montgomery u64 limbs, R = 2^256, fully reduced), the
  * unit everything above is built from             src/fields/fq/u64/wrapper.rs:99-132, fq/ops.rs

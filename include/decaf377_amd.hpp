@@ -138,6 +138,28 @@ class FixedBases {
     if (rc != D377_OK) throw DeviceError(rc);
     return enc;
   }
+  /// The same sums with every sum cut into segments of consecutive bases, one GPU lane per segment, where that fills the chip
+  /// (d377_batch_fixed_long_msm; long_plan shows the cut): few sums over many bases.  Any FixedBases, short or long.
+  std::vector<Encoding> msm_long(const std::vector<Fr>& scalars, std::vector<Element>* elements = nullptr) {
+    if (!h_) throw std::logic_error("decaf377_amd: FixedBases used after it was destroyed or its Engine was");
+    if (scalars.size() % m_) throw std::invalid_argument("length mismatch: scalars must be n x m");
+    std::vector<Encoding> enc(scalars.size() / m_);
+    if (elements) elements->assign(enc.size(), Element{});
+    const int rc = d377_batch_fixed_long_msm(ctx(), h_, reinterpret_cast<const uint8_t*>(scalars.data()), enc.size(),
+                                             reinterpret_cast<uint8_t*>(enc.data()),
+                                             elements ? reinterpret_cast<uint64_t*>(elements->data()) : nullptr);
+    if (rc != D377_OK) throw DeviceError(rc);
+    return enc;
+  }
+  /// {segments per sum, bases per segment} of msm_long for the slice of n sums that device `dev` of the Engine gets
+  /// (d377_fixed_long_msm_plan).
+  std::pair<size_t, size_t> long_plan(size_t n, int dev = 0) const {
+    if (!h_) throw std::logic_error("decaf377_amd: FixedBases used after it was destroyed or its Engine was");
+    uint64_t g = 0, b = 0;
+    const int rc = d377_fixed_long_msm_plan(ctx(), h_, n, dev, &g, &b);
+    if (rc != D377_OK) throw DeviceError(rc);
+    return {(size_t)g, (size_t)b};
+  }
   /// n sums of t terms that name their bases: sum i = sum over j < t of scalars[i t + j] * B_{base_index[i t + j]} (both
   /// term-major, n x t each).  An index is 0 .. size() - 1, or -1 for an absent term (which costs as much as a present
   /// one); anything else makes the library refuse the call (DeviceError, nothing computed).
@@ -206,6 +228,16 @@ class Engine {
     std::lock_guard<std::mutex> lock(fixed_mu_);
     fixed_.push_back(&fb);
     return fb;                                            // (moved out: the move constructor re-registers the new address)
+  }
+  /// Registers 1 .. 4096 fixed bases (D377_FIXED_BASES_LONG_MAX, d377_fixed_bases_create_long): 4096 bases are 2.2 GB at
+  /// comb_bits 8 and 22.5 GB at 12, per device.  vartime_multiscalar_mul on more than 64 bases is msm_long.
+  FixedBases fixed_bases_long(const std::vector<Element>& bases, int comb_bits = 12) {
+    int64_t h = 0;
+    check(d377_fixed_bases_create_long(ctx_, u64(bases), bases.size(), comb_bits, &h));
+    FixedBases fb(this, h, bases.size());
+    std::lock_guard<std::mutex> lock(fixed_mu_);
+    fixed_.push_back(&fb);
+    return fb;
   }
 
   /// Encoding::vartime_decompress, one Result per input (src/ark_curve/encoding.rs:32-83)

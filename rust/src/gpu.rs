@@ -141,6 +141,14 @@ impl<'a> FixedBases<'a> {
         check(unsafe { ffi::d377_fixed_bases_create(ctx.0, xyzt.as_ptr(), bases.len(), comb_bits, &mut handle) })?;
         Ok(Self { ctx, handle, m: bases.len() })
     }
+    /// 1..=4096 bases (d377_fixed_bases_create_long); `comb_bits` 8, 12, 16 or 18, 0 = 12.  4096 bases are 2.2 GB at 8 bits
+    /// and 22.5 GB at 12, per device.
+    pub fn new_long(ctx: &'a GpuContext, bases: &[Element], comb_bits: i32) -> Result<Self, GpuError> {
+        let xyzt = elements_to_xyzt(bases);
+        let mut handle = 0i64;
+        check(unsafe { ffi::d377_fixed_bases_create_long(ctx.0, xyzt.as_ptr(), bases.len(), comb_bits, &mut handle) })?;
+        Ok(Self { ctx, handle, m: bases.len() })
+    }
     /// (m, comb width in bits, table bytes per device)
     pub fn info(&self) -> Result<(u64, i32, u64), GpuError> {
         let (mut m, mut bits, mut bytes) = (0u64, 0i32, 0u64);
@@ -157,6 +165,19 @@ impl<'a> FixedBases<'a> {
         let mut out = vec![0u64; 16 * n];
         check(unsafe {
             ffi::d377_batch_fixed_msm(self.ctx.0, self.handle, bytes.as_ptr(), n, enc.as_mut_ptr() as *mut u8, out.as_mut_ptr())
+        })?;
+        Ok((enc, out.chunks_exact(16).map(element_from_xyzt).collect()))
+    }
+    /// The same sums with every sum cut into segments of consecutive bases, one GPU lane per segment, where that fills the
+    /// chip (d377_batch_fixed_long_msm): few sums over many bases.  Any `FixedBases`, short or long.
+    pub fn msm_long(&self, scalars: &[Fr]) -> Result<(Vec<Encoding>, Vec<Element>), GpuError> {
+        assert!(scalars.len() % self.m == 0);
+        let n = scalars.len() / self.m;
+        let bytes = pack32(scalars, |k| k.to_bytes());
+        let mut enc = vec![Encoding([0u8; 32]); n];
+        let mut out = vec![0u64; 16 * n];
+        check(unsafe {
+            ffi::d377_batch_fixed_long_msm(self.ctx.0, self.handle, bytes.as_ptr(), n, enc.as_mut_ptr() as *mut u8, out.as_mut_ptr())
         })?;
         Ok((enc, out.chunks_exact(16).map(element_from_xyzt).collect()))
     }
