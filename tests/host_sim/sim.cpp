@@ -106,6 +106,25 @@ Quad q_add(const Quad& v, const Quad& qrec, bool neg_q) {
 ge q_to_ge(const Quad& v) { ge g; g.x = v.l[0]; g.y = v.l[1]; g.z = v.l[2]; g.t = v.l[3]; return g; }
 }  // namespace
 
+// The comb walks' digits (curve.hpp fb_digit<BITS>) for the six widths the library builds combs of, as the kernels take them:
+// scalar mod r, halved mod r where the kernel halves (every Encoding-producing walk), the windows in order with the running
+// carry.  digits: n rows of 64 ints, FbShape<BITS>::windows used, [63] = the carry left after the top window (must be 0).
+// Returns the number of windows, or -1 for a width without a comb.
+template <int BITS>
+static int fb_digits_of(const uint32_t* k, size_t n, int halve, int* digits) {
+  constexpr int W = FbShape<BITS>::windows;
+  for (size_t i = 0; i < n; ++i) {
+    uint32_t w[8];
+    for (int j = 0; j < 8; ++j) w[j] = k[8 * i + j];
+    fr_reduce_words(w);
+    if (halve) fr_half_words(w);
+    uint32_t carry = 0;
+    for (int q = 0; q < W; ++q) digits[64 * i + q] = fb_digit<BITS>(w, q, carry);
+    digits[64 * i + 63] = (int)carry;
+  }
+  return W;
+}
+
 extern "C" {
 int sim_init() {
   // same construction the init kernels perform on the device
@@ -555,6 +574,40 @@ void sim_msm_digits(const uint32_t* k, size_t n, int c, int* shape, int* digits)
     uint32_t carry = 0;
     for (int q = 0; q < ws.W; ++q) digits[64 * i + q] = msm_digit(w, q, ws, carry);
     digits[64 * i + 63] = (int)carry;                   // must end as 0
+  }
+}
+// msm_digit on the words as given, neither reduced nor halved: its contract is any k < 2^252 (msm_plan.hpp), and that the top
+// window is not wrapped shows only above r -- a reduced scalar's top window stays below half its range.
+void sim_msm_digits_raw(const uint32_t* k, size_t n, int c, int* digits) {
+  const WinShape ws = win_shape(c);
+  for (size_t i = 0; i < n; ++i) {
+    uint32_t carry = 0;
+    for (int q = 0; q < ws.W; ++q) digits[64 * i + q] = msm_digit(k + 8 * i, q, ws, carry);
+    digits[64 * i + 63] = (int)carry;
+  }
+}
+// fb_digits_of<bits> (above) for the width asked for
+int sim_fb_digits(const uint32_t* k, size_t n, int bits, int halve, int* digits) {
+  switch (bits) {
+    case 8: return fb_digits_of<8>(k, n, halve, digits);
+    case 12: return fb_digits_of<12>(k, n, halve, digits);
+    case 16: return fb_digits_of<16>(k, n, halve, digits);
+    case 18: return fb_digits_of<18>(k, n, halve, digits);
+    case 21: return fb_digits_of<21>(k, n, halve, digits);
+    case 23: return fb_digits_of<23>(k, n, halve, digits);
+  }
+  return -1;
+}
+// The four-bit recoding of the Straus chains and the variable-base kernel (fr_recode_signed16) read back digit by digit
+// (fr_digit), scalar mod r and halved where the kernel halves.  digits: n rows of 64 ints, [63] = the carry window.
+void sim_w4_digits(const uint32_t* k, size_t n, int halve, int* digits) {
+  for (size_t i = 0; i < n; ++i) {
+    uint32_t w[8], dg[8];
+    for (int j = 0; j < 8; ++j) w[j] = k[8 * i + j];
+    fr_reduce_words(w);
+    if (halve) fr_half_words(w);
+    fr_recode_signed16(w, dg);
+    for (int q = 0; q < 64; ++q) digits[64 * i + q] = fr_digit(dg, q);
   }
 }
 // lanes that touch a bucket holding the entries [o, o + size) of its window when every lane takes L consecutive entries

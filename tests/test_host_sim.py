@@ -763,10 +763,14 @@ def test_to_affine_on_raw_records(sim, oracle):
 
 
 def test_msm_windows_digits_and_span_plan(sim):
-    """msm_plan.hpp, the code the MSM kernels run, on the host: (1) for every window width c = 4 .. 16 the windows -- the first
+    """msm_plan.hpp, the code the MSM kernels run, on the host: (1) for every window width c = 4 .. 18 the windows -- the first
     `nwide` c bits wide, the rest c - 1 -- tile the 252 scalar bits, and the signed digits of a scalar recompose to
     k / 2 mod r (the MSM sums with k / 2 and doubles at the end) with |digit| <= 2^(width - 1) and an unwrapped,
-    non-negative top digit inside the buckets of its width, for random, zero, tiny, near-r and all-ones scalars;
+    non-negative top digit inside the buckets of its width, for random, zero, tiny, near-r and all-ones scalars; for scalars
+    built from their digits (tests/_digit_cases.py: the last bucket -2^(w-1) and the largest positive digit of every window,
+    one window at a time and all at once, the top window's largest digit, all ones plus a carry; passed as 2 h mod r,
+    some with r added) and for the random ones the digit VECTOR is the big-integer restatement's, not merely its sum; on
+    unreduced words up to 2^252 - 1, msm_digit's whole domain, the top window stays unwrapped;
     (2) the span plan: with every lane taking L consecutive sorted entries, a bucket is touched by exactly the lanes the
     closed form names, and slot = lane + (non-empty buckets before) is strictly increasing along the entries -- no two
     partial sums share a slot."""
@@ -781,8 +785,28 @@ def test_msm_windows_digits_and_span_plan(sim):
     k[4] = 255
     k[5, 8:] = 0                                                   # a 64-bit scalar
     kw = np.ascontiguousarray(k).view(np.uint32).reshape(n, 8)
-    for c in range(4, 17):
+    import _digit_cases as dc
+    for c in range(4, 19):
         shape = np.zeros(2, np.int32)
+        layout = dc.msm(c)
+        cases = dc.msm_cases(c)
+        dc.assert_covers(layout, [h for _, _, h in cases])
+        tk = np.concatenate([dc.scalars([h for _, _, h in cases], True), dc.scalars([h for _, _, h in cases[::3]], True, plus_r=True)])
+        tw = np.ascontiguousarray(tk).view(np.uint32).reshape(len(tk), 8)
+        tdig = np.zeros((len(tk), 64), np.int32)
+        L.sim_msm_digits(tw.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(len(tk)), c, shape.ctypes.data_as(ctypes.c_void_p), tdig.ctypes.data_as(ctypes.c_void_p))
+        assert int(shape[0]) == len(layout)
+        for i, (name, d, _) in enumerate(cases + cases[::3]):
+            assert [int(x) for x in tdig[i, :len(layout)]] == d and tdig[i, 63] == 0, (c, name, i >= len(cases))
+        # the function's whole domain, k < 2^252, words as given: the top window at and above half its range stays unwrapped
+        fb_top, w_top = layout[-1]
+        raw = [(1 << 252) - 1, 1 << 251, (1 << 251) - 1, ((1 << (w_top - 1)) << fb_top) - 1, dc.R - 1, dc.R, dc.R + 1]
+        rk = np.stack([np.frombuffer(v.to_bytes(32, "little"), np.uint8) for v in raw]).view(np.uint32).reshape(len(raw), 8)
+        rdig = np.zeros((len(raw), 64), np.int32)
+        L.sim_msm_digits_raw(rk.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(len(raw)), c, rdig.ctypes.data_as(ctypes.c_void_p))
+        for i, v in enumerate(raw):
+            assert [int(x) for x in rdig[i, :len(layout)]] == dc.recode(layout, v) and rdig[i, 63] == 0, (c, hex(v))
+        assert rdig[0, len(layout) - 1] == 1 << w_top and rdig[1, len(layout) - 1] == 1 << (w_top - 1)
         dig = np.zeros((n, 64), np.int32)
         L.sim_msm_digits(kw.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(n), c, shape.ctypes.data_as(ctypes.c_void_p), dig.ctypes.data_as(ctypes.c_void_p))
         W, nwide = int(shape[0]), int(shape[1])
@@ -796,6 +820,7 @@ def test_msm_windows_digits_and_span_plan(sim):
             assert dig[i, 63] == 0 and sum(dv << first[w] for w, dv in enumerate(d)) == half, (c, i)
             assert all(abs(dv) <= 1 << (widths[w] - 1) for w, dv in enumerate(d)), (c, i)
             assert 0 <= d[W - 1] <= 1 << (widths[W - 1] - 1), (c, i)
+            assert d == dc.recode(layout, half), (c, i)
     # (2) the span plan on random bucket sizes (many empty, some huge), several L
     for trial in range(40):
         nb = int(rng.integers(1, 300))

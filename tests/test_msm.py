@@ -178,7 +178,7 @@ def test_msm_on_elements_from_every_producer(ctx, oracle):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("window", [4, 5, 6, 7, 9, 12, 13, 14, 15, 16, 17, 18])
+@pytest.mark.parametrize("window", [4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18])
 def test_msm_every_window_width(ctx, oracle, window):
     """Same inputs through different bucket widths (developer override) give the same bytes.  17 and 18 bits: int32 digits,
     the counting pass in 2 / 4 parts of the bucket range, 513 / 1 025 super-buckets, a middle level in the tree of bit-sums."""
