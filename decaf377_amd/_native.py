@@ -44,6 +44,7 @@ EXPORTS = [
     "d377_batch_fixed_msm_indexed",
     "d377_batch_msm_long", "d377_batch_msm_long_encoded",
     "d377_fixed_bases_create_long", "d377_batch_fixed_long_msm", "d377_fixed_long_msm_plan",
+    "d377_batch_msm_mixed", "d377_batch_msm_mixed_encoded",
 ]
 
 
@@ -204,9 +205,11 @@ def load():
     lib.d377_fixed_bases_create_long.argtypes = [vp, vp, sz, i32, ctypes.POINTER(ctypes.c_int64)]
     lib.d377_batch_fixed_long_msm.argtypes = [vp, ctypes.c_int64, vp, sz, vp, vp]
     lib.d377_fixed_long_msm_plan.argtypes = [vp, ctypes.c_int64, sz, i32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    lib.d377_batch_msm_mixed.argtypes = [vp, ctypes.c_int64, vp, vp, sz, vp, vp, sz, sz, vp, vp]
+    lib.d377_batch_msm_mixed_encoded.argtypes = [vp, ctypes.c_int64, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp]
     for name in ("d377_fixed_bases_create", "d377_fixed_bases_info", "d377_fixed_bases_destroy", "d377_batch_fixed_msm",
                  "d377_batch_fixed_msm_indexed", "d377_fixed_bases_create_long", "d377_batch_fixed_long_msm",
-                 "d377_fixed_long_msm_plan"):
+                 "d377_fixed_long_msm_plan", "d377_batch_msm_mixed", "d377_batch_msm_mixed_encoded"):
         getattr(lib, name).restype = i32
     _lib = lib
     return lib

@@ -423,6 +423,7 @@ void fixed_bases_release_all(d377_ctx* ctx) {
   }
   ctx->fixed.clear();
 }
+FixedBases* fixed_bases_find(d377_ctx* ctx, int64_t handle) { return find(ctx, handle); }
 }  // namespace d377
 
 extern "C" {

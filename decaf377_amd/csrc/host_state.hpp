@@ -113,6 +113,7 @@ struct DeviceState {
   int bml_lds[2] = {-1, -1};             // batch_msm_long.hip: LDS padding of its lane kernel (Element / Encoding form), -1 = not asked yet
   int fx_lds[4] = {-1, -1, -1, -1};      // fixed_bases.hip: LDS padding of its lane kernel per comb width (8 / 12 / 16 / 18), -1 = not asked yet
   int fxi_lds[4] = {-1, -1, -1, -1};     // the same for the lane kernel of the indexed sums
+  int bmx_lds[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};   // batch_msm_mixed.hip: LDS padding of its lane kernel, [Element / Encoding form][comb width], -1 = not asked yet
   uint32_t* gtab = nullptr;
   uint8_t* s_lookup = nullptr;
   uint32_t* fbase = nullptr;             // the fixed-base comb: null until built (d377.hip ensure_comb: at context creation, or by the first fixed-base call of a lazy context)
@@ -241,6 +242,8 @@ int debug_device_delay_ms();
 // Caller holds no lock; the context is being destroyed, so no other call may be running on it.
 struct FixedBases;
 void fixed_bases_release_all(d377_ctx* ctx);
+// fixed_bases.hip: the live registration `handle` of the context, or null (batch_msm_mixed.hip).  Caller holds ctx->mu.
+FixedBases* fixed_bases_find(d377_ctx* ctx, int64_t handle);
 
 }  // namespace d377
 

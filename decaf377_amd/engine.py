@@ -755,6 +755,78 @@ class FixedBases:
                 xyzt = torch.from_numpy(xyzt.view(np.int64)).to(tdev)
         return (enc, xyzt) if elements else enc
 
+    def msm_mixed(self, base_index, fixed_scalar32, points, var_scalar32, elements=False):
+        """n mixed sums, registered bases plus variable points (d377_batch_msm_mixed[_encoded]):
+
+            out[i] = sum over j < t of fixed[i t + j] * B_{base_index[i, j]}  +  sum over p < v of var[i v + p] * P[i v + p]
+
+        base_index: [n, t] int32 as in msm_indexed (-1 = absent, as costly as a present term), 1 <= t <= 64.
+        fixed_scalar32: [n * t, 32] or [n, t, 32] u8.  points: [n, v, 16] / [n * v, 16] u64 Element records, or [n, v, 32] /
+        [n * v, 32] u8 Encodings, 1 <= v <= 8.  var_scalar32: [n * v, 32] or [n, v, 32] u8.  Scalars are any 32 bytes, reduced
+        mod r.  -> enc [n, 32] u8, or (enc, xyzt [n, 16]) with elements=True; for Encodings status [n * v] u8 is appended
+        (1 = invalid Encoding, that term left out of its sum): msm_small's order.  A torch tensor is STAGED through host memory,
+        as in msm_indexed, and the results come back on the device of the first tensor among points, the scalars and the
+        indices.  An index outside -1 .. m-1 raises NativeError and nothing is computed."""
+        what = "FixedBases.msm_mixed"
+        h = self._live()
+        tdev = next((a.device for a in (points, var_scalar32, fixed_scalar32, base_index) if _is_torch(a)), None)
+        host = lambda a: np.asarray(a.detach().cpu().numpy() if _is_torch(a) else a)
+        idx = host(base_index)
+        if idx.ndim != 2 or idx.dtype.kind not in "iu":
+            raise ValueError(what + ": base_index must be an [n, t] integer array")
+        n, t = idx.shape
+        if idx.dtype != np.int32:
+            if idx.size and (int(idx.min()) < -(1 << 31) or int(idx.max()) >= (1 << 31)):
+                raise ValueError(what + ": base_index does not fit 32 bits")
+            idx = idx.astype(np.int32)
+        idx = np.ascontiguousarray(idx)
+        fs = np.ascontiguousarray(host(fixed_scalar32))
+        if fs.ndim == 3:
+            if fs.shape[:2] != (n, t):
+                raise ValueError(what + ": fixed scalars [n, t, 32] must match base_index [n, t]")
+            fs = fs.reshape(n * t, 32)
+        _check(fs, ENC, n * t, what + " fixed scalars")
+        pts = np.ascontiguousarray(host(points))
+        if pts.ndim == 3:
+            if pts.shape[0] != n:
+                raise ValueError(what + ": points [n, v, .] must have one row per sum")
+            pts = pts.reshape(pts.shape[0] * pts.shape[1], pts.shape[2])
+        encoded = pts.dtype == np.uint8
+        terms = _rows(pts)
+        if n == 0 or terms % n:
+            if terms or n:
+                raise ValueError(what + ": the number of points must be a multiple of the number of sums")
+        v = terms // n if n else 1
+        _check(pts, ENC if encoded else ELEM, n * v, what + " points")
+        vs = np.ascontiguousarray(host(var_scalar32))
+        if vs.ndim == 3:
+            if vs.shape[:2] != (n, v):
+                raise ValueError(what + ": variable scalars [n, v, 32] must match the points [n, v, .]")
+            vs = vs.reshape(n * v, 32)
+        _check(vs, ENC, n * v, what + " variable scalars")
+        enc = np.empty((n, 32), np.uint8)
+        xyzt = np.empty((n, 16), np.uint64) if elements else None
+        status = np.zeros((n * v,), np.uint8) if encoded else None
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        if encoded:
+            _native.check(self._lib.d377_batch_msm_mixed_encoded(self.ctx._h, h, p(idx), p(fs), ctypes.c_size_t(t), p(pts), p(vs),
+                                                                 ctypes.c_size_t(v), ctypes.c_size_t(n), p(enc),
+                                                                 p(xyzt) if elements else None, p(status)))
+        else:
+            _native.check(self._lib.d377_batch_msm_mixed(self.ctx._h, h, p(idx), p(fs), ctypes.c_size_t(t), p(pts), p(vs),
+                                                         ctypes.c_size_t(v), ctypes.c_size_t(n), p(enc), p(xyzt) if elements else None))
+        if tdev is not None:
+            import torch
+            enc = torch.from_numpy(enc).to(tdev)
+            if elements:
+                xyzt = torch.from_numpy(xyzt.view(np.int64)).to(tdev)
+            if encoded:
+                status = torch.from_numpy(status).to(tdev)
+        out = (enc, xyzt) if elements else (enc,)
+        if encoded:
+            out = out + (status,)
+        return out if len(out) > 1 else out[0]
+
     def vartime_multiscalar_mul(self, scalars):
         """The sums' Encodings for an Fr batch (or [n * m, 32] array) of n x m scalars, term-major within a sum."""
         return Encoding(self.msm(scalars.data if isinstance(scalars, _Bytes32) else scalars), self.ctx)

@@ -414,6 +414,49 @@ int d377_batch_fixed_long_msm(d377_ctx* ctx, int64_t handle, const uint8_t* scal
 int d377_fixed_long_msm_plan(d377_ctx* ctx, int64_t handle, size_t n, int dev, uint64_t* segments,
                              uint64_t* bases_per_segment);
 
+/* MANY mixed sums at once: registered bases plus variable points in one sum.  enc32_out[i] = the canonical Encoding of
+ *     sum over j < t of  fixed_scalar[i t + j] * B_{base_index[i t + j]}   +   sum over p < v of  var_scalar[i v + p] * P[i v + p]
+ * with 1 <= t <= D377_FIXED_BASES_MAX terms among the bases of `handle` and 1 <= v <= D377_BATCH_MSM_MIXED_MAX_VAR points of the
+ * sum's own: the check of a signature or a sigma protocol, R' = s B - c A (t = v = 1: what other curve libraries offer as
+ * vartime_double_scalar_mul_basepoint), and a commitment with an opening, v G_asset + r H + sum k_p P_p.  Every rule of
+ * d377_batch_fixed_msm_indexed holds for the fixed half and every rule of d377_batch_msm_small[_encoded] for the variable
+ * half: base_index is n x t ints, fixed_scalar32 n x t and var_scalar32 n x v 32-byte strings, the points n x v Element
+ * records (xyzt) or Encodings (enc32), all term-major within a sum; scalars are any 32 bytes, reduced mod r; index -1 is an
+ * absent term, which COSTS AS MUCH AS A PRESENT ONE; an index may repeat within a sum; any live handle works, short or long,
+ * with indices 0 .. m-1; an Element record with Z = 0 counts as the identity; _encoded reports an invalid Encoding in
+ * status[i v + p] and leaves only that term out; xyzt_out (optional) = the sums as Element records (some extended
+ * representative).  For t = 0 use d377_batch_msm_small, for v = 0 d377_batch_fixed_msm_indexed.
+ * One GPU lane computes a whole sum: the Straus chain of the small sums over its v points (252 doublings + 64 v additions +
+ * v tables), the comb walk of the indexed sums over its t terms (14-32 mixed additions each, no doubling), one addition that
+ * joins the two halves and one pass of the square-root-free compressor.  There is no wave-per-sum route: a small batch is
+ * as long as one chain.  Composed of existing calls the same sum is d377_batch_msm_small and d377_batch_fixed_msm_indexed
+ * with Element output, d377_batch_add and d377_batch_compress: four calls, and 128-byte records through host memory after
+ * each of the first three.
+ * Measured on one MI355X, host arrays, against that four-call composition in the same process, the two alternating, median of 5
+ * after 2 warm-ups with the min-to-max spread of each (profiles/msm_mixed_bench.json, tools/bench_msm_mixed.py), shapes
+ * (v, t, bases, comb_bits):  2^20 sums of (1, 1, 1, 16), the signature check: 25.3 ms against 117.6 ms (x 4.6; spreads 30.4 and
+ * 53.2 ms, one slow round each);  2^20 of (1, 2, 64, 16): 27.6 against 116.2 ms (x 4.2; spreads 27.5 and 50.8);  2^12 of the same
+ * two: 1.14 against 1.33 ms and 1.20 against 1.38 ms (x 1.17 and x 1.15; spreads below 0.09 ms).  USE THIS CALL for those: it is
+ * ahead by more than the two spreads.  For (3, 2, 64, 12) it is NOT established: 44.7 against 129.5 ms at 2^20 (x 2.9 by the
+ * medians, but the spreads, 30.3 and 97.5 ms, exceed the difference) and 1.82 against 1.89 ms at 2^12 (inside the spreads: a
+ * tie).  The Encodings of the two paths were equal in every case.  Kernel against kernel the lane kernel takes 17.1 / 18.1 / 28.5
+ * ms per 2^20 sums of the three shapes (profiles/msm_mixed_kernel_trace.txt), where the variable-base kernel alone takes 14.4 ms
+ * per 2^20 [k]P: at (1, 1) the Straus half on 192-byte table entries does not beat the leaner signed-limb chain, and the gain
+ * is the three calls and the Element records that no longer cross the bus.
+ * Arguments are checked in this order, all on the host before any copy or launch: v, t (D377_ERR_ARG, the message names the
+ * argument and the call that serves 0 of them), null buffers when n > 0 (the message names the buffer), ctx, the handle, then
+ * the whole n x t index array (the message names base_index and the first offending position); on a refused call no output
+ * byte is written; n == 0 with good arguments is D377_OK.  Scratch: the small sums' table scratch for v terms, grown on
+ * demand and kept.  A multi-GPU context slices the SUMS over its devices.  Host pointers only: a device-pointer form is not
+ * offered (a Python torch tensor is staged through host memory). */
+#define D377_BATCH_MSM_MIXED_MAX_VAR 8      /* = D377_BATCH_MSM_MAX_TERMS */
+int d377_batch_msm_mixed(d377_ctx* ctx, int64_t handle, const int* base_index, const uint8_t* fixed_scalar32, size_t t,
+                         const uint64_t* xyzt, const uint8_t* var_scalar32, size_t v, size_t n, uint8_t* enc32_out,
+                         uint64_t* xyzt_out);
+int d377_batch_msm_mixed_encoded(d377_ctx* ctx, int64_t handle, const int* base_index, const uint8_t* fixed_scalar32, size_t t,
+                                 const uint8_t* enc32, const uint8_t* var_scalar32, size_t v, size_t n, uint8_t* enc32_out,
+                                 uint64_t* xyzt_out, uint8_t* status);
+
 /* Fq field operations on in-memory elements (4 Montgomery u64 limbs, R = 2^256, fully reduced), the
  * unit everything above is built from             src/fields/fq/u64/wrapper.rs:99-132, fq/ops.rs
  * op: D377_FQ_ADD / SUB / MUL (binary, b != NULL) and D377_FQ_SQUARE / NEG / INVERSE (unary, b NULL).

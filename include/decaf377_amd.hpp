@@ -176,6 +176,48 @@ class FixedBases {
     if (rc != D377_OK) throw DeviceError(rc);
     return enc;
   }
+  /// n mixed sums: sum i = sum over j < t of fixed_scalars[i t + j] * B_{base_index[i t + j]} + sum over p < v of
+  /// var_scalars[i v + p] * points[i v + p] (d377_batch_msm_mixed; all term-major, 1 <= t <= 64, 1 <= v <= 8).  The check of a
+  /// signature R' = s B - c A is t = v = 1.  Index -1 is an absent term; any index outside -1 .. size() - 1 makes the library
+  /// refuse the call (DeviceError, nothing computed).
+  std::vector<Encoding> msm_mixed(const std::vector<int>& base_index, const std::vector<Fr>& fixed_scalars, size_t t,
+                                  const std::vector<Element>& points, const std::vector<Fr>& var_scalars, size_t v,
+                                  std::vector<Element>* elements = nullptr) {
+    if (!h_) throw std::logic_error("decaf377_amd: FixedBases used after it was destroyed or its Engine was");
+    if (t == 0 || v == 0 || fixed_scalars.size() % t || base_index.size() != fixed_scalars.size() || points.size() % v ||
+        var_scalars.size() != points.size() || points.size() / v != fixed_scalars.size() / t)
+      throw std::invalid_argument("length mismatch: base_index and fixed_scalars must be n x t, points and var_scalars n x v");
+    std::vector<Encoding> enc(fixed_scalars.size() / t);
+    if (elements) elements->assign(enc.size(), Element{});
+    const int rc = d377_batch_msm_mixed(ctx(), h_, base_index.data(), reinterpret_cast<const uint8_t*>(fixed_scalars.data()), t,
+                                        reinterpret_cast<const uint64_t*>(points.data()),
+                                        reinterpret_cast<const uint8_t*>(var_scalars.data()), v, enc.size(),
+                                        reinterpret_cast<uint8_t*>(enc.data()),
+                                        elements ? reinterpret_cast<uint64_t*>(elements->data()) : nullptr);
+    if (rc != D377_OK) throw DeviceError(rc);
+    return enc;
+  }
+  /// The same sums over Encodings (d377_batch_msm_mixed_encoded): status[i v + p] = 1 marks an invalid Encoding, whose term
+  /// alone is left out of its sum.
+  std::vector<Encoding> msm_mixed(const std::vector<int>& base_index, const std::vector<Fr>& fixed_scalars, size_t t,
+                                  const std::vector<Encoding>& points, const std::vector<Fr>& var_scalars, size_t v,
+                                  std::vector<uint8_t>* status, std::vector<Element>* elements = nullptr) {
+    if (!h_) throw std::logic_error("decaf377_amd: FixedBases used after it was destroyed or its Engine was");
+    if (t == 0 || v == 0 || fixed_scalars.size() % t || base_index.size() != fixed_scalars.size() || points.size() % v ||
+        var_scalars.size() != points.size() || points.size() / v != fixed_scalars.size() / t)
+      throw std::invalid_argument("length mismatch: base_index and fixed_scalars must be n x t, points and var_scalars n x v");
+    std::vector<Encoding> enc(fixed_scalars.size() / t);
+    std::vector<uint8_t> st(points.size(), 0);
+    if (elements) elements->assign(enc.size(), Element{});
+    const int rc = d377_batch_msm_mixed_encoded(ctx(), h_, base_index.data(), reinterpret_cast<const uint8_t*>(fixed_scalars.data()), t,
+                                                reinterpret_cast<const uint8_t*>(points.data()),
+                                                reinterpret_cast<const uint8_t*>(var_scalars.data()), v, enc.size(),
+                                                reinterpret_cast<uint8_t*>(enc.data()),
+                                                elements ? reinterpret_cast<uint64_t*>(elements->data()) : nullptr, st.data());
+    if (rc != D377_OK) throw DeviceError(rc);
+    if (status) status->swap(st);
+    return enc;
+  }
   /// table bytes per device
   uint64_t table_bytes() const {
     uint64_t b = 0;

@@ -195,6 +195,44 @@ impl<'a> FixedBases<'a> {
         })?;
         Ok((enc, out.chunks_exact(16).map(element_from_xyzt).collect()))
     }
+    /// n mixed sums: sum i = sum over j < t of fixed_scalars[i t + j] * B_{base_index[i t + j]} + sum over p < v of
+    /// var_scalars[i v + p] * points[i v + p] (d377_batch_msm_mixed; all term-major, 1 <= t <= 64, 1 <= v <= 8).  The check
+    /// of a signature R' = s B - c A is t = v = 1.  Index -1 is an absent term; any other index outside 0..m is refused by
+    /// the library before anything is computed.  `want_elements`: also return the sums as Elements (128 bytes per sum more
+    /// come back from the device); otherwise the second vector is empty.
+    pub fn msm_mixed(&self, base_index: &[i32], fixed_scalars: &[Fr], t: usize, points: &[Element], var_scalars: &[Fr], v: usize, want_elements: bool) -> Result<(Vec<Encoding>, Vec<Element>), GpuError> {
+        let n = Self::mixed_len(base_index, fixed_scalars, t, points.len(), var_scalars, v);
+        let fixed = pack32(fixed_scalars, |k| k.to_bytes());
+        let var = pack32(var_scalars, |k| k.to_bytes());
+        let xyzt = elements_to_xyzt(points);
+        let mut enc = vec![Encoding([0u8; 32]); n];
+        let mut out = vec![0u64; if want_elements { 16 * n } else { 0 }];
+        let out_ptr = if want_elements { out.as_mut_ptr() } else { std::ptr::null_mut() };
+        check(unsafe {
+            ffi::d377_batch_msm_mixed(self.ctx.0, self.handle, base_index.as_ptr(), fixed.as_ptr(), t, xyzt.as_ptr(), var.as_ptr(), v, n, enc.as_mut_ptr() as *mut u8, out_ptr)
+        })?;
+        Ok((enc, out.chunks_exact(16).map(element_from_xyzt).collect()))
+    }
+    /// The same sums with the points as Encodings (d377_batch_msm_mixed_encoded): status[i v + p] = 1 marks an invalid
+    /// Encoding, whose term alone is left out of its sum.  -> (Encodings, Elements or empty, status).
+    pub fn msm_mixed_encoded(&self, base_index: &[i32], fixed_scalars: &[Fr], t: usize, points: &[Encoding], var_scalars: &[Fr], v: usize, want_elements: bool) -> Result<(Vec<Encoding>, Vec<Element>, Vec<u8>), GpuError> {
+        let n = Self::mixed_len(base_index, fixed_scalars, t, points.len(), var_scalars, v);
+        let fixed = pack32(fixed_scalars, |k| k.to_bytes());
+        let var = pack32(var_scalars, |k| k.to_bytes());
+        let mut enc = vec![Encoding([0u8; 32]); n];
+        let mut out = vec![0u64; if want_elements { 16 * n } else { 0 }];
+        let out_ptr = if want_elements { out.as_mut_ptr() } else { std::ptr::null_mut() };
+        let mut status = vec![0u8; n * v];
+        check(unsafe {
+            ffi::d377_batch_msm_mixed_encoded(self.ctx.0, self.handle, base_index.as_ptr(), fixed.as_ptr(), t, enc_ptr(points), var.as_ptr(), v, n, enc.as_mut_ptr() as *mut u8, out_ptr, status.as_mut_ptr())
+        })?;
+        Ok((enc, out.chunks_exact(16).map(element_from_xyzt).collect(), status))
+    }
+    fn mixed_len(base_index: &[i32], fixed_scalars: &[Fr], t: usize, points: usize, var_scalars: &[Fr], v: usize) -> usize {
+        assert!(t > 0 && v > 0 && fixed_scalars.len() % t == 0 && base_index.len() == fixed_scalars.len());
+        assert!(points % v == 0 && var_scalars.len() == points && points / v == fixed_scalars.len() / t);
+        fixed_scalars.len() / t
+    }
 }
 impl Drop for FixedBases<'_> {
     fn drop(&mut self) {
