@@ -1,0 +1,108 @@
+// batch_host.hpp -- the host launch path the batched-sum units share (batch_msm.hip, batch_msm_long.hip, batch_msm_mixed.hip,
+// fixed_bases.hip): the residency check of a lane kernel, the Straus table scratch, the chunk deal of a lane-set kernel and
+// the frame of one device's slice of a host-pointer call.  (The fan-out over the devices is host_state.hpp's
+// slice_over_devices.)  Everything here runs under ctx->mu.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+#include "dcb.hpp"
+#include "straus.hpp"
+#include "host_state.hpp"
+
+namespace d377 {
+
+// Residency of a lane kernel against the lane sets (as d377_ctx_create checks the kernels of d377.hip): at most
+// WAVES_PER_SIMD workgroups per CU, padded with dynamic LDS where registers alone would let more in.  Once per device and
+// instantiation: `lds` is that kernel's cache in DeviceState (-1 = not asked yet) and receives the padding.
+inline int lane_residency(const void* fn, const char* name, int bits, int& lds) {
+  if (lds >= 0) return D377_OK;
+  int nb = 0;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, 0));
+  int pad = 0;
+  if (nb > WAVES_PER_SIMD) {
+    pad = (160 * 1024) / (WAVES_PER_SIMD + 1) + 1024;
+    if (pad > 64 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, pad));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, (size_t)pad));
+  }
+  if (getenv("D377_DEBUG_RESIDENCY"))
+    fprintf(stderr, "d377: %s<%d>: %d workgroups per CU with %d bytes of LDS padding\n", name, bits, nb, pad);
+  if (nb < 1 || nb > WAVES_PER_SIMD)
+    return fail(D377_ERR_INIT, "residency of %s does not match the lane sets of the scratch areas", name);
+  lds = pad;
+  return D377_OK;
+}
+
+// The Straus table scratch d.bm_scratch for `terms` tables per resident lane (straus_tab.hpp: the tables, then the digit
+// words), grown if it is smaller: *tab and *dig are the two parts.  The area may not grow inside a stream capture
+// (D377_ERR_ARG, text `in_capture`); a failed allocation is D377_ERR_HIP with text `no_memory`.  Launches on `s`; the caller
+// holds the scope of the lane-set guard (GuardScope on d.vb_guard), not yet acquired.
+inline int straus_scratch_reserve(DeviceState& d, hipStream_t s, size_t terms, const char* in_capture, const char* no_memory,
+                                  uint32_t** tab, uint32_t** dig) {
+  const size_t tab_words = d.resident_lanes() * terms * VB_ENTRIES * BM_ENTRY_WORDS;
+  const size_t need = (tab_words + d.resident_lanes() * BM_WINDOWS) * sizeof(uint32_t);
+  if (need > d.bm_cap) {
+    if (ScratchGuard::capturing(s)) return fail(D377_ERR_ARG, "%s", in_capture);
+    int rc;
+    if ((rc = d.vb_guard.drain())) return rc;               // a launch on another stream may still be using the old area
+    if (d.bm_scratch) HIP_TRY(hipFree(d.bm_scratch));
+    d.bm_scratch = nullptr; d.bm_cap = 0;
+    if (hipMalloc(&d.bm_scratch, need) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(D377_ERR_HIP, "%s", no_memory);
+    }
+    d.bm_cap = need;
+  }
+  *tab = d.bm_scratch;
+  *dig = d.bm_scratch + tab_words;
+  return D377_OK;
+}
+
+// The chunks of a lane-set kernel over `count` elements (deal_chunks): the launch's grid and its DcbScratch.  A launch of at
+// most two generations of workgroups asks for issue priority by progress (dcb.hpp), as d377.hip's chunks_of.
+inline DcbScratch lane_chunks(const DeviceState& d, size_t count, int* grid) {
+  const size_t places = (size_t)d.cus * WAVES_PER_SIMD;
+  const ChunkDeal c = deal_chunks((count + BLOCK - 1) / BLOCK, places, (size_t)DCB_K, (size_t)d.cus * 64);
+  DcbScratch dcb{d.dcb_scratch, d.slot_pool, d.cus * WAVES_PER_SIMD, (int)c.per_lane, d.dcb_sets * BLOCK, (int)c.extra, d.pool_health};
+  dcb.prio = c.nchunks <= 2 * places ? 1 : 0;
+  *grid = (int)c.nchunks;
+  return dcb;
+}
+
+// One device's slice of a host-pointer call: body() stages the inputs, launches on d.stream and enqueues the copies out; the
+// frame selects the device, brackets the body with the starvation check, synchronises and gives the verdict.  On an error
+// nothing is left in flight (SyncOnError).
+template <class Body>
+int device_slice(DeviceState& d, Body&& body) {
+  HIP_TRY(hipSetDevice(d.id));
+  int rc = D377_OK;
+  SyncOnError guard{&rc, d.id, d.stream, nullptr};
+  rc = [&]() -> int {
+    StarveCheck starve{d, d.stream};
+    int r;
+    if ((r = starve.before())) return r;
+    if ((r = body())) return r;
+    if ((r = starve.after())) return r;
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    return starve.verdict();
+  }();
+  return rc;
+}
+
+// The staging of a slice's outputs in buf[2]: n Encodings, then n Element records if the caller wants them (*xyzt_dev, else null).
+inline int sums_out_reserve(DeviceState& d, size_t n, bool want_xyzt, uint64_t** xyzt_dev) {
+  int rc;
+  if ((rc = ensure(d, 2, n * (want_xyzt ? 32 + 128 : 32)))) return rc;
+  *xyzt_dev = want_xyzt ? reinterpret_cast<uint64_t*>(d.buf[2] + n * 32) : nullptr;
+  return D377_OK;
+}
+// ... and their copies to the caller, enqueued on d.stream
+inline int sums_out_copy(DeviceState& d, size_t n, uint8_t* out32, uint64_t* xyzt_out) {
+  HIP_TRY(hipMemcpyAsync(out32, d.buf[2], n * 32, hipMemcpyDeviceToHost, d.stream));
+  if (xyzt_out) HIP_TRY(hipMemcpyAsync(xyzt_out, d.buf[2] + n * 32, n * 128, hipMemcpyDeviceToHost, d.stream));
+  return D377_OK;
+}
+
+}  // namespace d377

@@ -24,10 +24,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <chrono>
-#include <string>
-#include <thread>
-#include <vector>
 
 #include "../../include/decaf377_amd.h"
 #include "curve.hpp"
@@ -36,7 +32,9 @@
 #include "quad_ops.hpp"
 #include "row_ops.hpp"
 #include "straus.hpp"
+#include "straus_tab.hpp"
 #include "host_state.hpp"
+#include "batch_host.hpp"
 #include "codec_chunked.hpp"
 #include "batch_msm_long_plan.hpp"
 #include "msm_long_fold.hpp"
@@ -48,30 +46,6 @@ namespace {
 constexpr size_t BML_MAX = D377_BATCH_MSM_LONG_MAX_TERMS;
 static_assert(BML_GROUP_MAX == D377_BATCH_MSM_MAX_TERMS, "a group is one chain of the small sums");
 static_assert(VB_ENTRIES == 9, "straus_sum stores entries 0 .. 8 of every point's table");
-
-// batch_msm.hip's StrausTab, restated (that unit keeps its source): the scratch of one resident lane, tables
-// [point][entry][lane] and digit words [window][lane]
-struct StrausTab {
-  uint32_t* tab;
-  uint32_t* dig;
-  size_t nthreads, tid;
-  __device__ __forceinline__ uint32_t* entry(int p, int j) const { return tab + (((size_t)p * VB_ENTRIES + j) * nthreads + tid) * BM_ENTRY_WORDS; }
-  __device__ __forceinline__ void store(int p, int j, const gec& c) {
-    uint32_t* q = entry(p, j);
-    slot_store(q, c.ypx); slot_store(q + SLOT, c.ymx); slot_store(q + 2 * SLOT, c.z2); slot_store(q + 3 * SLOT, c.kt);
-  }
-  __device__ __forceinline__ gec load(int p, int j, bool swap) const {
-    const uint32_t* q = entry(p, j);
-    gec c;
-    c.ypx = slot_load(q + (swap ? SLOT : 0));
-    c.ymx = slot_load(q + (swap ? 0 : SLOT));
-    c.z2 = slot_load(q + 2 * SLOT);
-    c.kt = slot_load(q + 3 * SLOT);
-    return c;
-  }
-  __device__ __forceinline__ void dig_store(int w, uint32_t v) { dig[(size_t)w * nthreads + tid] = v; }
-  __device__ __forceinline__ uint32_t dig_load(int w) const { return dig[(size_t)w * nthreads + tid]; }
-};
 
 // ---- one lane per partial sum -----------------------------------------------------------------------------------------------
 // np = n g partial sums; partial p = s g + q reads the terms from s m + q b.  status: one byte per TERM, written for live slots only.
@@ -112,10 +86,9 @@ k_msm_long_lane(SqrtTables T, const void* pts_in, const uint8_t* scalar32, LongP
   D377_DCB_END();
 }
 
-// ---- one wave per partial sum: batch_msm.hip's k_batch_msm_wave on a group, without the compressor --------------------------
+// ---- one wave per partial sum: straus_tab.hpp's chain on a group, without the compressor --------------------------------------
 // The chain's term count is uniform over the workgroup, so the wave form runs the group's live terms only: it has no dead slots.
 using row::RQ_WORDS;
-static_assert(POW_TAB * 64 <= row::RQ_TAB_ENTRIES * RQ_WORDS, "row_sqrt_powers' scratch must fit in one point's LDS table");
 template <bool ENCODED>
 __global__ void __launch_bounds__(64)
 k_msm_long_wave(SqrtTables T, const void* pts_in, const uint8_t* scalar32, LongPlan plan, size_t np, uint64_t* partials,
@@ -123,73 +96,12 @@ k_msm_long_wave(SqrtTables T, const void* pts_in, const uint8_t* scalar32, LongP
   extern __shared__ uint32_t tab[];                                // b tables of RQ_TAB_ENTRIES x RQ_WORDS words (dynamic: 2 304 bytes per term)
   __shared__ uint32_t xrec[2 * RQ_WORDS];
   __shared__ uint32_t sdg[BML_GROUP_MAX][8];                       // the points' signed digits (wave-uniform reads in the loop)
-  const int t = threadIdx.x;
-  const row::RowK K = row::row_consts();
-  const row::RowSel S = row::row_sel();
   const size_t part = blockIdx.x;                                  // grid = np
   if (part >= np) return;
   const size_t gq = part % plan.g;
-  const size_t first = (part / plan.g) * plan.m + plan.first(gq);
-  const int m = (int)plan.count(gq);
-#pragma unroll 1
-  for (int base = 0; base < m; base += 4) {
-    const int pj = t & 3;
-    const bool mine = base + pj < m;
-    const size_t e_mine = first + (size_t)(mine ? base + pj : 0);
-    ge g;
-    bool skip = !mine;
-    if (ENCODED) {
-      uint32_t w[8];
-      load32(reinterpret_cast<const uint8_t*>(pts_in), e_mine, w);
-      if (t < 4) row::row_store_from_fe(xrec + 16 * t, ge_decompress_den(w));
-      __syncthreads();
-      const row::RowPowers pw = row::row_sqrt_powers(xrec[t], tab + base * row::RQ_TAB_ENTRIES * RQ_WORDS, t, K);   // (this group's tables: not built yet)
-      __syncthreads();
-      xrec[t] = pw.v; xrec[RQ_WORDS + t] = pw.uv;
-      __syncthreads();
-      const fe pv = row::row_load_to_fe(xrec + 16 * pj), puv = row::row_load_to_fe(xrec + RQ_WORDS + 16 * pj);
-      __syncthreads();
-      const uint32_t bad = ge_decompress_from_powers(T, w, pv, puv, &g);
-      if (t < 4 && mine) status[e_mine] = (uint8_t)bad;
-      skip |= bad != 0;
-    } else {
-      g = load_ge_mont256(reinterpret_cast<const uint64_t*>(pts_in), e_mine);
-      skip |= fe_is_zero(g.z);
-      D377_INVARIANT(T, g, t < 4 && !skip);
-    }
-#pragma unroll 1
-    for (int j = 0; j < 4 && base + j < m; ++j) {
-      uint32_t k[8], dg[8];
-      load32(scalar32, first + (size_t)(base + j), k);
-      fr_reduce_words(k);
-      fr_half_words(k);
-      fr_recode_signed16(k, dg);
-      if (pj == j && t < 16) row::row_store_from_fe(xrec + 16 * (t >> 2), fe_pick(t >> 2, g.x, g.y, g.z, g.t));
-      __syncthreads();
-      const bool dead = __shfl((int)skip, j) != 0;                  // (wave-uniform: lane j's verdict on point base + j)
-      if (t < 8) sdg[base + j][t] = dead ? 0u : dg[t];              // dead: every digit 0
-      row::rq_build_table(dead ? row::rq_identity(S) : xrec[t], tab + (base + j) * row::RQ_TAB_ENTRIES * RQ_WORDS, S, K);
-      __syncthreads();
-    }
-  }
-  uint32_t v = row::rq_identity(S);
-#pragma unroll 1
-  for (int i = 63; i >= 0; --i) {
-    if (i != 63) {
-#pragma unroll 1
-      for (int k = 0; k < 4; ++k) v = row::rq_double_neg(v, S, K);  // four sign-folded doublings keep the sign
-    }
-#pragma unroll 1
-    for (int j = 0; j < m; ++j) {
-      const int d = fr_digit(sdg[j], i);
-      if (d != 0) v = row::rq_add(v, tab + (j * row::RQ_TAB_ENTRIES + (d < 0 ? -d : d)) * RQ_WORDS, S, d < 0, K);
-    }
-  }
-  __syncthreads();
-  xrec[t] = v;
-  __syncthreads();
-  const ge r = row::rq_load_point(xrec);
-  if (t == 0) store_ge_mont256(partials, part, ge_double_fast(r, true));
+  const ge r = straus_wave_sum<ENCODED>(T, pts_in, scalar32, (part / plan.g) * plan.m + plan.first(gq), (int)plan.count(gq), status,
+                                        tab, xrec, sdg);
+  if (threadIdx.x == 0) store_ge_mont256(partials, part, ge_double_fast(r, true));
 }
 
 // ---- the fold: c records per sum -> ceil(c / BML_FOLD) ------------------------------------------------------------------------
@@ -276,12 +188,10 @@ int long_sums_fold_compress(DeviceState& d, hipStream_t s, size_t n, size_t g, u
     turn ^= 1;
   }
 
-  // ---- the sums' Encodings, in chunks with batched inversions (codec_chunked.hip); the chunks as batch_msm_launch deals them
-  const size_t places = (size_t)d.cus * WAVES_PER_SIMD;
-  const ChunkDeal c = deal_chunks((n + BLOCK - 1) / BLOCK, places, (size_t)DCB_K, (size_t)d.cus * 64);
-  DcbScratch dcb{d.dcb_scratch, d.slot_pool, d.cus * WAVES_PER_SIMD, (int)c.per_lane, d.dcb_sets * BLOCK, (int)c.extra, d.pool_health};
-  dcb.prio = c.nchunks <= 2 * places ? 1 : 0;
-  return codec_chunked_launch(d, s, false, cur, n, out32, nullptr, (int)c.nchunks, dcb);
+  // ---- the sums' Encodings, in chunks with batched inversions (codec_chunked.hip)
+  int grid;
+  const DcbScratch dcb = lane_chunks(d, n, &grid);
+  return codec_chunked_launch(d, s, false, cur, n, out32, nullptr, grid, dcb);
 }
 
 }  // namespace d377
@@ -301,16 +211,8 @@ int batch_msm_long_launch(DeviceState& d, hipStream_t s, bool encoded, const voi
   int rc;
   uint64_t* partials = nullptr;
   if ((rc = long_sums_partials(d, s, n, plan.g, &partials))) return rc;
-  const size_t places = (size_t)d.cus * WAVES_PER_SIMD;
-  auto deal = [&](size_t count, int& grid) {                 // the chunks of a lane-set kernel over `count` elements (as batch_msm_launch)
-    const ChunkDeal c = deal_chunks((count + BLOCK - 1) / BLOCK, places, (size_t)DCB_K, (size_t)d.cus * 64);
-    DcbScratch dcb{d.dcb_scratch, d.slot_pool, d.cus * WAVES_PER_SIMD, (int)c.per_lane, d.dcb_sets * BLOCK, (int)c.extra, d.pool_health};
-    dcb.prio = c.nchunks <= 2 * places ? 1 : 0;
-    grid = (int)c.nchunks;
-    return dcb;
-  };
 
-  // ---- phase 1: the chains.  The route by the number of PARTIAL sums, batch_msm_launch's rule: up to four per SIMD a wave each
+  // ---- phase 1: the chains.  The route by the number of PARTIAL sums, batch_msm.hip's rule: up to four per SIMD a wave each
   const size_t wave_max = 4 * (size_t)d.tuned(D377_TUNE_TINY_MAX, (long long)d.cus * 4);
   if (np <= wave_max) {
     if ((rc = vb.acquire())) return rc;
@@ -319,41 +221,17 @@ int batch_msm_long_launch(DeviceState& d, hipStream_t s, bool encoded, const voi
     else hipLaunchKernelGGL(k_msm_long_wave<false>, dim3((unsigned)np), dim3(64), lds, s, T, pts_in, scalars, plan, np, partials, status);
     HIP_TRY(hipGetLastError());
   } else {
-    // residency of the lane kernel against the lane sets, once per device (as batch_msm_launch)
     const void* fn = encoded ? reinterpret_cast<const void*>(k_msm_long_lane<true>) : reinterpret_cast<const void*>(k_msm_long_lane<false>);
     int& lds = d.bml_lds[encoded ? 1 : 0];
-    if (lds < 0) {
-      int nb = 0;
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, 0));
-      int pad = 0;
-      if (nb > WAVES_PER_SIMD) {
-        pad = (160 * 1024) / (WAVES_PER_SIMD + 1) + 1024;
-        if (pad > 64 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, pad));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, (size_t)pad));
-      }
-      if (nb < 1 || nb > WAVES_PER_SIMD)
-        return fail(D377_ERR_INIT, "residency of %s does not match the lane sets of the scratch areas", "k_msm_long_lane");
-      lds = pad;
-    }
-    // the table scratch of the small sums' lane kernel, grown as batch_msm_launch grows it, for b terms per lane
-    const size_t need = d.resident_lanes() * (plan.b * VB_ENTRIES * BM_ENTRY_WORDS + BM_WINDOWS) * sizeof(uint32_t);
-    if (need > d.bm_cap) {
-      if (ScratchGuard::capturing(s))
-        return fail(D377_ERR_ARG, "%s", "batch_msm_long: the table scratch must grow, which cannot happen inside a stream capture");
-      if ((rc = d.vb_guard.drain())) return rc;
-      if (d.bm_scratch) HIP_TRY(hipFree(d.bm_scratch));
-      d.bm_scratch = nullptr; d.bm_cap = 0;
-      if (hipMalloc(&d.bm_scratch, need) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(D377_ERR_HIP, "%s", "batch_msm_long: hipMalloc of the table scratch failed (0.23 GB per term of a group on 256 CUs)");
-      }
-      d.bm_cap = need;
-    }
+    if ((rc = lane_residency(fn, "k_msm_long_lane", encoded, lds))) return rc;
+    // the table scratch of the small sums' lane kernel, for b terms per lane
+    uint32_t *tab, *dig;
+    if ((rc = straus_scratch_reserve(d, s, plan.b,
+           "batch_msm_long: the table scratch must grow, which cannot happen inside a stream capture",
+           "batch_msm_long: hipMalloc of the table scratch failed (0.23 GB per term of a group on 256 CUs)", &tab, &dig))) return rc;
     if ((rc = vb.acquire())) return rc;
-    int grid = 0;
-    const DcbScratch dcb = deal(np, grid);
-    uint32_t* tab = d.bm_scratch;
-    uint32_t* dig = tab + d.resident_lanes() * plan.b * VB_ENTRIES * BM_ENTRY_WORDS;
+    int grid;
+    const DcbScratch dcb = lane_chunks(d, np, &grid);
     if (encoded)
       hipLaunchKernelGGL(k_msm_long_lane<true>, dim3((unsigned)grid), dim3(BLOCK), lds, s, T, pts_in, scalars, plan, np, partials, status, tab, dig, dcb);
     else
@@ -366,35 +244,25 @@ int batch_msm_long_launch(DeviceState& d, hipStream_t s, bool encoded, const voi
   return vb.finish();
 }
 
-// one device's slice of a host batch: copies in, kernels, copies out, synchronised (as batch_msm.hip's batch_msm_one)
+// one device's slice of a host batch: copies in, kernels, copies out, synchronised
 int batch_msm_long_one(DeviceState& d, bool encoded, const uint8_t* pts_in, const uint8_t* scalars, size_t m, size_t n, uint8_t* out32,
                        uint64_t* xyzt_out, uint8_t* status) {
   if (n == 0) return D377_OK;
-  HIP_TRY(hipSetDevice(d.id));
-  int rc = D377_OK;
-  SyncOnError guard{&rc, d.id, d.stream, nullptr};
-  auto body = [&]() -> int {
+  return device_slice(d, [&]() -> int {
     const size_t rec = encoded ? 32 : 128, terms = n * m;
     int r;
+    uint64_t* xyzt_dev;
     if ((r = ensure(d, 0, terms * rec))) return r;
     if ((r = ensure(d, 1, terms * 32))) return r;
-    if ((r = ensure(d, 2, n * (xyzt_out ? 32 + 128 : 32)))) return r;      // the Encodings, then the Element records
+    if ((r = sums_out_reserve(d, n, xyzt_out != nullptr, &xyzt_dev))) return r;
     if (encoded && (r = ensure(d, 3, terms))) return r;
-    StarveCheck starve{d, d.stream};
-    if ((r = starve.before())) return r;
     HIP_TRY(hipMemcpyAsync(d.buf[0], pts_in, terms * rec, hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipMemcpyAsync(d.buf[1], scalars, terms * 32, hipMemcpyHostToDevice, d.stream));
-    uint64_t* xyzt_dev = xyzt_out ? reinterpret_cast<uint64_t*>(d.buf[2] + n * 32) : nullptr;
     if ((r = batch_msm_long_launch(d, d.stream, encoded, d.buf[0], d.buf[1], m, n, d.buf[2], xyzt_dev, d.buf[3]))) return r;
-    HIP_TRY(hipMemcpyAsync(out32, d.buf[2], n * 32, hipMemcpyDeviceToHost, d.stream));
-    if (xyzt_out) HIP_TRY(hipMemcpyAsync(xyzt_out, xyzt_dev, n * 128, hipMemcpyDeviceToHost, d.stream));
+    if ((r = sums_out_copy(d, n, out32, xyzt_out))) return r;
     if (encoded) HIP_TRY(hipMemcpyAsync(status, d.buf[3], terms, hipMemcpyDeviceToHost, d.stream));
-    if ((r = starve.after())) return r;
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    return starve.verdict();
-  };
-  rc = body();
-  return rc;
+    return D377_OK;
+  });
 }
 
 // host pointers.  The checks come in the documented order -- m, null buffers (n > 0), ctx -- and before any device is touched.
@@ -414,29 +282,12 @@ int batch_msm_long_host(d377_ctx* ctx, bool encoded, const void* pts_in, const u
     return encoded ? d377_batch_msm_small_encoded(ctx, (const uint8_t*)pts_in, scalars, m, n, out32, xyzt_out, status)
                    : d377_batch_msm_small(ctx, (const uint64_t*)pts_in, scalars, m, n, out32, xyzt_out);
   std::lock_guard<std::mutex> lock(ctx->mu);
-  const size_t nd = ctx->devs.size(), rec = encoded ? 32 : 128;
-  if (nd == 1) return batch_msm_long_one(ctx->devs[0], encoded, (const uint8_t*)pts_in, scalars, m, n, out32, xyzt_out, status);
-  // contiguous slices of the SUMS over the context's devices, one host thread per device (as batch_msm_host)
-  const size_t per = (n + nd - 1) / nd;
-  std::vector<int> rcs(nd, D377_OK);
-  std::vector<std::string> errs(nd);
-  std::vector<std::thread> workers;
-  const int delay = debug_device_delay_ms();
-  for (size_t k = 0; k < nd; ++k) {
-    const size_t lo = per * k;
-    if (lo >= n) break;
-    const size_t cnt = (lo + per <= n) ? per : n - lo;
-    workers.emplace_back([&, k, lo, cnt]() {
-      if (delay > 0) std::this_thread::sleep_for(std::chrono::milliseconds(delay));
-      rcs[k] = batch_msm_long_one(ctx->devs[k], encoded, (const uint8_t*)pts_in + lo * m * rec, scalars + lo * m * 32, m, cnt, out32 + lo * 32,
-                                  xyzt_out ? xyzt_out + lo * 16 : nullptr, encoded ? status + lo * m : nullptr);
-      if (rcs[k] != D377_OK) errs[k] = d377_g_err;
-    });
-  }
-  for (auto& w : workers) w.join();
-  for (size_t k = 0; k < nd; ++k)
-    if (rcs[k] != D377_OK) return fail(rcs[k], "%s", errs[k].c_str());
-  return D377_OK;
+  const size_t rec = encoded ? 32 : 128;
+  // contiguous slices of the SUMS over the context's devices (host_state.hpp: slice_over_devices)
+  return slice_over_devices(ctx, n, [&](size_t k, size_t lo, size_t cnt) {
+    return batch_msm_long_one(ctx->devs[k], encoded, (const uint8_t*)pts_in + lo * m * rec, scalars + lo * m * 32, m, cnt, out32 + lo * 32,
+                              xyzt_out ? xyzt_out + lo * 16 : nullptr, encoded ? status + lo * m : nullptr);
+  });
 }
 
 }  // namespace

@@ -22,20 +22,18 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <chrono>
 #include <mutex>
-#include <string>
-#include <thread>
-#include <type_traits>
-#include <vector>
 
 #include "../../include/decaf377_amd.h"
 #include "curve.hpp"
 #include "device_util.hpp"
 #include "dcb.hpp"
 #include "straus.hpp"
+#include "straus_tab.hpp"
+#include "comb_tabs.hpp"
 #include "mixed_sum.hpp"
 #include "host_state.hpp"
+#include "batch_host.hpp"
 
 using namespace d377;
 
@@ -45,39 +43,6 @@ constexpr int MX_VAR_MAX = D377_BATCH_MSM_MIXED_MAX_VAR;
 constexpr int MX_FIXED_MAX = D377_FIXED_BASES_MAX;
 static_assert(MX_VAR_MAX == D377_BATCH_MSM_MAX_TERMS && MX_VAR_MAX == 8, "a window's digits of the v points of a sum are the eight nibbles of one word");
 static_assert(VB_ENTRIES == 9, "straus_sum stores entries 0 .. 8 of every point's table");
-
-// batch_msm.hip's StrausTab, restated (that unit keeps its source): the scratch of one resident lane, tables
-// [point][entry][lane] and digit words [window][lane]
-struct StrausTab {
-  uint32_t* tab;
-  uint32_t* dig;
-  size_t nthreads, tid;
-  __device__ __forceinline__ uint32_t* entry(int p, int j) const { return tab + (((size_t)p * VB_ENTRIES + j) * nthreads + tid) * BM_ENTRY_WORDS; }
-  __device__ __forceinline__ void store(int p, int j, const gec& c) {
-    uint32_t* q = entry(p, j);
-    slot_store(q, c.ypx); slot_store(q + SLOT, c.ymx); slot_store(q + 2 * SLOT, c.z2); slot_store(q + 3 * SLOT, c.kt);
-  }
-  __device__ __forceinline__ gec load(int p, int j, bool swap) const {
-    const uint32_t* q = entry(p, j);
-    gec c;
-    c.ypx = slot_load(q + (swap ? SLOT : 0));
-    c.ymx = slot_load(q + (swap ? 0 : SLOT));
-    c.z2 = slot_load(q + 2 * SLOT);
-    c.kt = slot_load(q + 3 * SLOT);
-    return c;
-  }
-  __device__ __forceinline__ void dig_store(int w, uint32_t v) { dig[(size_t)w * nthreads + tid] = v; }
-  __device__ __forceinline__ uint32_t dig_load(int w) const { return dig[(size_t)w * nthreads + tid]; }
-};
-
-// fixed_bases.hip's CombTabs, restated: the m combs of a handle, back to back: entry c of window i of base j
-template <int BITS>
-struct CombTabs {
-  const uint32_t* base;
-  __device__ __forceinline__ gea load(int j, int i, int c, bool swap) const {
-    return pt_load_affine(base + (((size_t)j * FbShape<BITS>::windows + i) * FbShape<BITS>::entries + c) * FBW_ENTRY_WORDS, swap);
-  }
-};
 
 // One lane per sum.  The variable half is k_batch_msm_lane's body, the fixed half k_fixed_msm_indexed_lane's: an absent term
 // (-1) walks scalar 0 on comb 0, and the unsigned compare treats every index outside 0 .. m-1 as absent, so no index can
@@ -129,23 +94,6 @@ k_batch_msm_mixed_lane(SqrtTables T, const uint32_t* tabs, const int* base_index
 }
 
 // ------------------------------------------------------------------------------ host side ---
-int width_slot(int bits) { return bits == 8 ? 0 : bits == 12 ? 1 : bits == 16 ? 2 : bits == 18 ? 3 : -1; }
-template <class F>
-int with_width(int bits, F&& f) {
-  switch (bits) {
-    case 8: return f(std::integral_constant<int, 8>{});
-    case 12: return f(std::integral_constant<int, 12>{});
-    case 16: return f(std::integral_constant<int, 16>{});
-    case 18: return f(std::integral_constant<int, 18>{});
-  }
-  return fail(D377_ERR_ARG, "%s", "batch_msm_mixed: the registration's comb width is none of 8, 12, 16, 18");
-}
-
-// bytes of scratch per resident lane for v variable terms (batch_msm.hip's layout: the area is the same)
-size_t scratch_bytes(const DeviceState& d, int v) {
-  return d.resident_lanes() * ((size_t)v * VB_ENTRIES * BM_ENTRY_WORDS + BM_WINDOWS) * sizeof(uint32_t);
-}
-
 struct MixedArgs {
   const uint32_t* combs;       // the handle's combs on this device
   int m, bits;
@@ -162,52 +110,26 @@ struct MixedArgs {
 int mixed_launch(DeviceState& d, hipStream_t s, const MixedArgs& a, size_t n, uint8_t* out32, uint64_t* xyzt_out, uint8_t* status) {
   if (n == 0) return D377_OK;
   const SqrtTables T = d.tables();
-  return with_width(a.bits, [&](auto bb) -> int {
+  return with_width(a.bits, "batch_msm_mixed: the registration's comb width is none of 8, 12, 16, 18", [&](auto bb) -> int {
     constexpr int BITS = decltype(bb)::value;
-    // residency of the lane kernel against the lane sets (as batch_msm.hip's), once per device and instantiation
     const void* fn = a.encoded ? reinterpret_cast<const void*>(k_batch_msm_mixed_lane<BITS, true>)
                                : reinterpret_cast<const void*>(k_batch_msm_mixed_lane<BITS, false>);
     int& lds = d.bmx_lds[a.encoded ? 1 : 0][width_slot(BITS)];
-    if (lds < 0) {
-      int nb = 0;
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, 0));
-      int pad = 0;
-      if (nb > WAVES_PER_SIMD) {
-        pad = (160 * 1024) / (WAVES_PER_SIMD + 1) + 1024;
-        if (pad > 64 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, pad));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, (size_t)pad));
-      }
-      if (nb < 1 || nb > WAVES_PER_SIMD)
-        return fail(D377_ERR_INIT, "residency of %s does not match the lane sets of the scratch areas", "k_batch_msm_mixed_lane");
-      lds = pad;
-    }
-    GuardScope vb{d.vb_guard, s};                            // the lane-set areas and the table scratch: queue behind their last user
     int rc;
-    const size_t need = scratch_bytes(d, (int)a.v);
-    if (need > d.bm_cap) {
-      if (ScratchGuard::capturing(s))
-        return fail(D377_ERR_ARG, "%s", "batch_msm_mixed: the table scratch must grow, which cannot happen inside a stream capture");
-      if ((rc = d.vb_guard.drain())) return rc;             // a launch on another stream may still be using the old area
-      if (d.bm_scratch) HIP_TRY(hipFree(d.bm_scratch));
-      d.bm_scratch = nullptr; d.bm_cap = 0;
-      if (hipMalloc(&d.bm_scratch, need) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(D377_ERR_HIP, "%s", "batch_msm_mixed: hipMalloc of the table scratch failed (0.23 GB per variable term on 256 CUs)");
-      }
-      d.bm_cap = need;
-    }
+    if ((rc = lane_residency(fn, "k_batch_msm_mixed_lane", BITS, lds))) return rc;
+    GuardScope vb{d.vb_guard, s};                            // the lane-set areas and the table scratch: queue behind their last user
+    uint32_t *tab, *dig;
+    if ((rc = straus_scratch_reserve(d, s, a.v,
+           "batch_msm_mixed: the table scratch must grow, which cannot happen inside a stream capture",
+           "batch_msm_mixed: hipMalloc of the table scratch failed (0.23 GB per variable term on 256 CUs)", &tab, &dig))) return rc;
     if ((rc = vb.acquire())) return rc;
-    const size_t places = (size_t)d.cus * WAVES_PER_SIMD, rounds = (n + BLOCK - 1) / BLOCK;
-    const ChunkDeal c = deal_chunks(rounds, places, (size_t)DCB_K, (size_t)d.cus * 64);
-    DcbScratch dcb{d.dcb_scratch, d.slot_pool, d.cus * WAVES_PER_SIMD, (int)c.per_lane, d.dcb_sets * BLOCK, (int)c.extra, d.pool_health};
-    dcb.prio = c.nchunks <= 2 * places ? 1 : 0;             // as d377.hip's chunks_of
-    uint32_t* tab = d.bm_scratch;
-    uint32_t* dig = tab + d.resident_lanes() * a.v * VB_ENTRIES * BM_ENTRY_WORDS;
+    int grid;
+    const DcbScratch dcb = lane_chunks(d, n, &grid);
     if (a.encoded)
-      hipLaunchKernelGGL((k_batch_msm_mixed_lane<BITS, true>), dim3((unsigned)c.nchunks), dim3(BLOCK), lds, s, T, a.combs, a.index,
+      hipLaunchKernelGGL((k_batch_msm_mixed_lane<BITS, true>), dim3((unsigned)grid), dim3(BLOCK), lds, s, T, a.combs, a.index,
                          a.fixed_scalars, a.m, (int)a.t, a.pts_in, a.var_scalars, (int)a.v, n, out32, xyzt_out, status, tab, dig, dcb);
     else
-      hipLaunchKernelGGL((k_batch_msm_mixed_lane<BITS, false>), dim3((unsigned)c.nchunks), dim3(BLOCK), lds, s, T, a.combs, a.index,
+      hipLaunchKernelGGL((k_batch_msm_mixed_lane<BITS, false>), dim3((unsigned)grid), dim3(BLOCK), lds, s, T, a.combs, a.index,
                          a.fixed_scalars, a.m, (int)a.t, a.pts_in, a.var_scalars, (int)a.v, n, out32, xyzt_out, status, tab, dig, dcb);
     HIP_TRY(hipGetLastError());
     return vb.finish();
@@ -221,41 +143,31 @@ int mixed_one(DeviceState& d, const FixedBases& fb, const uint32_t* combs, const
               bool encoded, const uint8_t* pts_in, const uint8_t* var_scalars, size_t v, size_t n, uint8_t* out32,
               uint64_t* xyzt_out, uint8_t* status) {
   if (n == 0) return D377_OK;
-  HIP_TRY(hipSetDevice(d.id));
-  int rc = D377_OK;
-  SyncOnError guard{&rc, d.id, d.stream, nullptr};
-  auto body = [&]() -> int {
+  return device_slice(d, [&]() -> int {
     const size_t rec = encoded ? 32 : 128, vterms = n * v, fterms = n * t;
     // fixed scalars | indices (padded to 16 bytes) | variable scalars
     const size_t idx_off = fterms * 32, var_off = idx_off + ((fterms * sizeof(int) + 15) & ~(size_t)15);
     int r;
+    uint64_t* xyzt_dev;
     if ((r = ensure(d, 0, vterms * rec))) return r;
     if ((r = ensure(d, 1, var_off + vterms * 32))) return r;
-    if ((r = ensure(d, 2, n * (xyzt_out ? 32 + 128 : 32)))) return r;      // the Encodings, then the Element records
+    if ((r = sums_out_reserve(d, n, xyzt_out != nullptr, &xyzt_dev))) return r;
     if (encoded && (r = ensure(d, 3, vterms))) return r;
-    StarveCheck starve{d, d.stream};
-    if ((r = starve.before())) return r;
     HIP_TRY(hipMemcpyAsync(d.buf[0], pts_in, vterms * rec, hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipMemcpyAsync(d.buf[1], fixed_scalars, fterms * 32, hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipMemcpyAsync(d.buf[1] + idx_off, index, fterms * sizeof(int), hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipMemcpyAsync(d.buf[1] + var_off, var_scalars, vterms * 32, hipMemcpyHostToDevice, d.stream));
-    uint64_t* xyzt_dev = xyzt_out ? reinterpret_cast<uint64_t*>(d.buf[2] + n * 32) : nullptr;
     const MixedArgs a{combs, (int)fb.m, fb.bits, reinterpret_cast<const int*>(d.buf[1] + idx_off), d.buf[1], t, encoded, d.buf[0],
                       d.buf[1] + var_off, v};
     if ((r = mixed_launch(d, d.stream, a, n, d.buf[2], xyzt_dev, d.buf[3]))) return r;
-    HIP_TRY(hipMemcpyAsync(out32, d.buf[2], n * 32, hipMemcpyDeviceToHost, d.stream));
-    if (xyzt_out) HIP_TRY(hipMemcpyAsync(xyzt_out, xyzt_dev, n * 128, hipMemcpyDeviceToHost, d.stream));
+    if ((r = sums_out_copy(d, n, out32, xyzt_out))) return r;
     if (encoded) HIP_TRY(hipMemcpyAsync(status, d.buf[3], vterms, hipMemcpyDeviceToHost, d.stream));
-    if ((r = starve.after())) return r;
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    return starve.verdict();
-  };
-  rc = body();
-  return rc;
+    return D377_OK;
+  });
 }
 
 // host pointers: every argument checked before any copy or launch, then contiguous slices of the SUMS over the context's
-// devices, one host thread per device (as batch_msm.hip)
+// devices (host_state.hpp: slice_over_devices)
 int mixed_host(const char* who, d377_ctx* ctx, int64_t handle, const int* base_index, const uint8_t* fixed_scalar32, size_t t,
                bool encoded, const void* pts_in, const uint8_t* var_scalar32, size_t v, size_t n, uint8_t* enc32_out,
                uint64_t* xyzt_out, uint8_t* status) {
@@ -289,31 +201,13 @@ int mixed_host(const char* who, d377_ctx* ctx, int64_t handle, const int* base_i
     }
   }
   if (n == 0) return D377_OK;
-  const size_t nd = ctx->devs.size(), rec = encoded ? 32 : 128;
+  const size_t rec = encoded ? 32 : 128;
   const uint8_t* pts = reinterpret_cast<const uint8_t*>(pts_in);
-  if (nd == 1)
-    return mixed_one(ctx->devs[0], *fb, fb->tab[0], base_index, fixed_scalar32, t, encoded, pts, var_scalar32, v, n, enc32_out, xyzt_out, status);
-  const size_t per = (n + nd - 1) / nd;
-  std::vector<int> rcs(nd, D377_OK);
-  std::vector<std::string> errs(nd);
-  std::vector<std::thread> workers;
-  const int delay = debug_device_delay_ms();
-  for (size_t k = 0; k < nd; ++k) {
-    const size_t lo = per * k;
-    if (lo >= n) break;
-    const size_t cnt = (lo + per <= n) ? per : n - lo;
-    workers.emplace_back([&, k, lo, cnt]() {
-      if (delay > 0) std::this_thread::sleep_for(std::chrono::milliseconds(delay));
-      rcs[k] = mixed_one(ctx->devs[k], *fb, fb->tab[k], base_index + lo * t, fixed_scalar32 + lo * t * 32, t, encoded, pts + lo * v * rec,
-                         var_scalar32 + lo * v * 32, v, cnt, enc32_out + lo * 32, xyzt_out ? xyzt_out + lo * 16 : nullptr,
-                         encoded ? status + lo * v : nullptr);
-      if (rcs[k] != D377_OK) errs[k] = d377_g_err;
-    });
-  }
-  for (auto& w : workers) w.join();
-  for (size_t k = 0; k < nd; ++k)
-    if (rcs[k] != D377_OK) return fail(rcs[k], "%s", errs[k].c_str());
-  return D377_OK;
+  return slice_over_devices(ctx, n, [&](size_t k, size_t lo, size_t cnt) {
+    return mixed_one(ctx->devs[k], *fb, fb->tab[k], base_index + lo * t, fixed_scalar32 + lo * t * 32, t, encoded, pts + lo * v * rec,
+                     var_scalar32 + lo * v * 32, v, cnt, enc32_out + lo * 32, xyzt_out ? xyzt_out + lo * 16 : nullptr,
+                     encoded ? status + lo * v : nullptr);
+  });
 }
 
 }  // namespace

@@ -13,7 +13,6 @@
 #include <chrono>
 #include <mutex>
 #include <new>
-#include <string>
 #include <thread>
 #include <type_traits>
 #include <vector>
@@ -1989,38 +1988,17 @@ int run_one(DeviceState& d, Op op, int aux, const OpShape& sh, const void* in0, 
   return rc;
 }
 
-// host-pointer path: contiguous slices over the context's devices.  With several devices each slice is
-// driven by its own host thread: copies from pageable caller memory block the issuing thread, so a single
-// thread would run the devices one after another.
+// host-pointer path: contiguous slices over the context's devices (host_state.hpp: slice_over_devices)
 int run_host(d377_ctx* ctx, Op op, int aux, const void* in0, const void* in1, size_t n, void* out0, void* out1) {
   if (!ctx) return fail(D377_ERR_ARG, "%s", "null context");
   const OpShape sh = shape_of(op);
   if (n && (!in0 || (sh.in1 && !in1) || !out0 || (sh.out1 && !out1))) return fail(D377_ERR_ARG, "%s", "null buffer");
   if (n == 0) return D377_OK;
   std::lock_guard<std::mutex> lock(ctx->mu);
-  const size_t nd = ctx->devs.size();
-  if (nd == 1) return run_one(ctx->devs[0], op, aux, sh, in0, in1, n, out0, out1);
-  const size_t per = (n + nd - 1) / nd;
-  std::vector<int> rcs(nd, D377_OK);
-  std::vector<std::string> errs(nd);
-  std::vector<std::thread> workers;
-  const int delay = debug_device_delay_ms();
-  for (size_t k = 0; k < nd; ++k) {
-    const size_t lo = per * k;
-    if (lo >= n) break;
-    const size_t cnt = (lo + per <= n) ? per : n - lo;
-    workers.emplace_back([&, k, lo, cnt]() {
-      if (delay > 0) std::this_thread::sleep_for(std::chrono::milliseconds(delay));
-      rcs[k] = run_one(ctx->devs[k], op, aux, sh, (const uint8_t*)in0 + lo * sh.in0,
-                       sh.in1 ? (const uint8_t*)in1 + lo * sh.in1 : nullptr, cnt, (uint8_t*)out0 + lo * sh.out0,
-                       sh.out1 ? (uint8_t*)out1 + lo * sh.out1 : nullptr);
-      if (rcs[k] != D377_OK) errs[k] = d377_g_err;       // the worker's thread-local text
-    });
-  }
-  for (auto& w : workers) w.join();                      // every device has drained before we return, error or not
-  for (size_t k = 0; k < nd; ++k)
-    if (rcs[k] != D377_OK) return fail(rcs[k], "%s", errs[k].c_str());
-  return D377_OK;
+  return slice_over_devices(ctx, n, [&](size_t k, size_t lo, size_t cnt) {
+    return run_one(ctx->devs[k], op, aux, sh, (const uint8_t*)in0 + lo * sh.in0, sh.in1 ? (const uint8_t*)in1 + lo * sh.in1 : nullptr, cnt,
+                   (uint8_t*)out0 + lo * sh.out0, sh.out1 ? (uint8_t*)out1 + lo * sh.out1 : nullptr);
+  });
 }
 
 int check_dev_args(d377_ctx* ctx, int dev, Op op, const void* in0, const void* in1, size_t n, const void* out0,

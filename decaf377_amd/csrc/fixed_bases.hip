@@ -22,12 +22,8 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
-#include <chrono>
 #include <mutex>
 #include <new>
-#include <string>
-#include <thread>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/decaf377_amd.h"
@@ -35,7 +31,9 @@
 #include "device_util.hpp"
 #include "dcb.hpp"
 #include "host_state.hpp"
+#include "batch_host.hpp"
 #include "fixed_comb.hpp"
+#include "comb_tabs.hpp"
 #include "codec_chunked.hpp"
 #include "fixed_msm_long_plan.hpp"
 #include "msm_long_fold.hpp"
@@ -47,15 +45,6 @@ namespace {
 constexpr int FX_MAX = D377_FIXED_BASES_MAX;
 constexpr int FX_LONG_MAX = D377_FIXED_BASES_LONG_MAX;
 static_assert(FX_LONG_MAX <= 4096, "g <= m segments must fold in three levels of BML_FOLD = 16");
-
-// the m combs of a handle, back to back: entry c of window i of base j
-template <int BITS>
-struct CombTabs {
-  const uint32_t* base;
-  __device__ __forceinline__ gea load(int j, int i, int c, bool swap) const {
-    return pt_load_affine(base + (((size_t)j * FbShape<BITS>::windows + i) * FbShape<BITS>::entries + c) * FBW_ENTRY_WORDS, swap);
-  }
-};
 
 // One lane per sum, in chunks like k_scalar_mul_base (dcb.hpp): the sums of a chunk share one inversion per wave.  No table
 // scratch -- the combs are the handle's -- so the lane sets are only the round records.
@@ -156,48 +145,19 @@ k_fixed_msm_seg(SqrtTables T, const uint32_t* tabs, const uint8_t* scalar32, Fix
 }
 
 // ------------------------------------------------------------------------------ host side ---
-// The comb widths a handle may ask for; f(std::integral_constant<int, BITS>) runs with the kernels of that width.
-int width_slot(int bits) { return bits == 8 ? 0 : bits == 12 ? 1 : bits == 16 ? 2 : bits == 18 ? 3 : -1; }
-template <class F>
-int with_width(int bits, F&& f) {
-  switch (bits) {
-    case 8: return f(std::integral_constant<int, 8>{});
-    case 12: return f(std::integral_constant<int, 12>{});
-    case 16: return f(std::integral_constant<int, 16>{});
-    case 18: return f(std::integral_constant<int, 18>{});
-  }
-  return fail(D377_ERR_ARG, "%s", "d377_fixed_bases_create: comb_bits must be 8, 12, 16 or 18 (0 = 16)");
-}
+// what with_width (comb_tabs.hpp) says to a width no registration can have
+constexpr const char* WIDTH_REFUSAL = "d377_fixed_bases_create: comb_bits must be 8, 12, 16 or 18 (0 = 16)";
 template <int BITS>
 size_t comb_bytes() { return (size_t)FbShape<BITS>::windows * FbShape<BITS>::entries * FBW_ENTRY_WORDS * sizeof(uint32_t); }
 
-// Residency of the two lane kernels against the lane sets (as d377_ctx_create checks the kernels of d377.hip): at most
-// WAVES_PER_SIMD workgroups per CU, padded with dynamic LDS where registers alone would let more in.  Once per device and
-// width, by d377_fixed_bases_create; the caller holds ctx->mu.
-int check_residency_of(const void* fn, const char* name, int bits, int& lds);
+// Residency of the two lane kernels against the lane sets (batch_host.hpp), once per device and width, by
+// d377_fixed_bases_create; the caller holds ctx->mu.
 template <int BITS>
 int check_residency_fx(DeviceState& d) {
-  int rc = check_residency_of(reinterpret_cast<const void*>(k_fixed_msm_lane<BITS>), "k_fixed_msm_lane", BITS, d.fx_lds[width_slot(BITS)]);
+  int rc = lane_residency(reinterpret_cast<const void*>(k_fixed_msm_lane<BITS>), "k_fixed_msm_lane", BITS, d.fx_lds[width_slot(BITS)]);
   if (rc) return rc;
-  return check_residency_of(reinterpret_cast<const void*>(k_fixed_msm_indexed_lane<BITS>), "k_fixed_msm_indexed_lane", BITS,
-                            d.fxi_lds[width_slot(BITS)]);
-}
-int check_residency_of(const void* fn, const char* name, int bits, int& lds) {
-  if (lds >= 0) return D377_OK;
-  int nb = 0;
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, 0));
-  int pad = 0;
-  if (nb > WAVES_PER_SIMD) {
-    pad = (160 * 1024) / (WAVES_PER_SIMD + 1) + 1024;
-    if (pad > 64 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, pad));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, (size_t)pad));
-  }
-  if (getenv("D377_DEBUG_RESIDENCY"))
-    fprintf(stderr, "d377: %s<%d>: %d workgroups per CU with %d bytes of LDS padding\n", name, bits, nb, pad);
-  if (nb < 1 || nb > WAVES_PER_SIMD)
-    return fail(D377_ERR_INIT, "residency of %s does not match the lane sets of the scratch areas", name);
-  lds = pad;
-  return D377_OK;
+  return lane_residency(reinterpret_cast<const void*>(k_fixed_msm_indexed_lane<BITS>), "k_fixed_msm_indexed_lane", BITS,
+                        d.fxi_lds[width_slot(BITS)]);
 }
 
 // the combs of `m` bases on one device: residency check, allocation, window bases, one build launch, synchronised.
@@ -256,17 +216,15 @@ int fixed_msm_launch(DeviceState& d, hipStream_t s, const FixedBases& fb, const 
   GuardScope vb{d.vb_guard, s};                              // the lane-set areas: queue behind their last user
   int rc;
   if ((rc = vb.acquire())) return rc;
-  const size_t places = (size_t)d.cus * WAVES_PER_SIMD, rounds = (n + BLOCK - 1) / BLOCK;
-  const ChunkDeal c = deal_chunks(rounds, places, (size_t)DCB_K, (size_t)d.cus * 64);
-  DcbScratch dcb{d.dcb_scratch, d.slot_pool, d.cus * WAVES_PER_SIMD, (int)c.per_lane, d.dcb_sets * BLOCK, (int)c.extra, d.pool_health};
-  dcb.prio = c.nchunks <= 2 * places ? 1 : 0;               // as d377.hip's chunks_of
+  int grid;
+  const DcbScratch dcb = lane_chunks(d, n, &grid);
   const SqrtTables T = d.tables();
-  if ((rc = with_width(fb.bits, [&](auto b) -> int {
+  if ((rc = with_width(fb.bits, WIDTH_REFUSAL, [&](auto b) -> int {
          if (index)
-           hipLaunchKernelGGL(k_fixed_msm_indexed_lane<decltype(b)::value>, dim3((unsigned)c.nchunks), dim3(BLOCK), lds, s, T, tab,
+           hipLaunchKernelGGL(k_fixed_msm_indexed_lane<decltype(b)::value>, dim3((unsigned)grid), dim3(BLOCK), lds, s, T, tab,
                               index, scalars, (int)fb.m, (int)t, n, out32, xyzt_out, dcb);
          else
-           hipLaunchKernelGGL(k_fixed_msm_lane<decltype(b)::value>, dim3((unsigned)c.nchunks), dim3(BLOCK), lds, s, T, tab, scalars,
+           hipLaunchKernelGGL(k_fixed_msm_lane<decltype(b)::value>, dim3((unsigned)grid), dim3(BLOCK), lds, s, T, tab, scalars,
                               (int)fb.m, n, out32, xyzt_out, dcb);
          return D377_OK; }))) return rc;
   HIP_TRY(hipGetLastError());
@@ -293,7 +251,7 @@ int fixed_msm_long_launch(DeviceState& d, hipStream_t s, const FixedBases& fb, c
   size_t grid = (n * plan.g + BLOCK - 1) / BLOCK;
   if (grid > (size_t)d.cus * 8) grid = (size_t)d.cus * 8;    // (as the fold's)
   const SqrtTables T = d.tables();
-  if ((rc = with_width(fb.bits, [&](auto b) -> int {
+  if ((rc = with_width(fb.bits, WIDTH_REFUSAL, [&](auto b) -> int {
          hipLaunchKernelGGL(k_fixed_msm_seg<decltype(b)::value>, dim3((unsigned)grid), dim3(BLOCK), 0, s, T, tab, scalars, plan, n, partials);
          return D377_OK; }))) return rc;
   HIP_TRY(hipGetLastError());
@@ -306,60 +264,31 @@ int fixed_msm_long_launch(DeviceState& d, hipStream_t s, const FixedBases& fb, c
 int fixed_msm_one(DeviceState& d, const FixedBases& fb, const uint32_t* tab, const int* index, size_t t, bool cut, const uint8_t* scalars,
                   size_t n, uint8_t* out32, uint64_t* xyzt_out) {
   if (n == 0) return D377_OK;
-  HIP_TRY(hipSetDevice(d.id));
-  int rc = D377_OK;
-  SyncOnError guard{&rc, d.id, d.stream, nullptr};
-  auto body = [&]() -> int {
+  return device_slice(d, [&]() -> int {
     const size_t terms = n * t;
     int r;
+    uint64_t* xyzt_dev;
     if ((r = ensure(d, 1, terms * 32 + (index ? terms * sizeof(int) : 0)))) return r;
-    if ((r = ensure(d, 2, n * (xyzt_out ? 32 + 128 : 32)))) return r;      // the Encodings, then the Element records
-    StarveCheck starve{d, d.stream};
-    if ((r = starve.before())) return r;
+    if ((r = sums_out_reserve(d, n, xyzt_out != nullptr, &xyzt_dev))) return r;
     HIP_TRY(hipMemcpyAsync(d.buf[1], scalars, terms * 32, hipMemcpyHostToDevice, d.stream));
     const int* index_dev = index ? reinterpret_cast<const int*>(d.buf[1] + terms * 32) : nullptr;
     if (index) HIP_TRY(hipMemcpyAsync(d.buf[1] + terms * 32, index, terms * sizeof(int), hipMemcpyHostToDevice, d.stream));
-    uint64_t* xyzt_dev = xyzt_out ? reinterpret_cast<uint64_t*>(d.buf[2] + n * 32) : nullptr;
     if (cut) r = fixed_msm_long_launch(d, d.stream, fb, tab, d.buf[1], n, d.buf[2], xyzt_dev);
     else r = fixed_msm_launch(d, d.stream, fb, tab, index_dev, t, d.buf[1], n, d.buf[2], xyzt_dev);
     if (r) return r;
-    HIP_TRY(hipMemcpyAsync(out32, d.buf[2], n * 32, hipMemcpyDeviceToHost, d.stream));
-    if (xyzt_out) HIP_TRY(hipMemcpyAsync(xyzt_out, xyzt_dev, n * 128, hipMemcpyDeviceToHost, d.stream));
-    if ((r = starve.after())) return r;
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    return starve.verdict();
-  };
-  rc = body();
-  return rc;
+    return sums_out_copy(d, n, out32, xyzt_out);
+  });
 }
 
-// n sums in contiguous slices over the context's devices, one host thread per device (as batch_msm.hip); t terms per sum,
+// n sums in contiguous slices over the context's devices (host_state.hpp: slice_over_devices); t terms per sum,
 // index == null for the dense sums, which `cut` has every device cut into segments.  Caller holds ctx->mu.
 int fixed_msm_sliced(d377_ctx* ctx, const FixedBases& fb, const int* index, size_t t, bool cut, const uint8_t* scalar32, size_t n,
                      uint8_t* enc32_out, uint64_t* xyzt_out) {
   if (n == 0) return D377_OK;
-  const size_t nd = ctx->devs.size();
-  if (nd == 1) return fixed_msm_one(ctx->devs[0], fb, fb.tab[0], index, t, cut, scalar32, n, enc32_out, xyzt_out);
-  const size_t per = (n + nd - 1) / nd;
-  std::vector<int> rcs(nd, D377_OK);
-  std::vector<std::string> errs(nd);
-  std::vector<std::thread> workers;
-  const int delay = debug_device_delay_ms();
-  for (size_t k = 0; k < nd; ++k) {
-    const size_t lo = per * k;
-    if (lo >= n) break;
-    const size_t cnt = (lo + per <= n) ? per : n - lo;
-    workers.emplace_back([&, k, lo, cnt]() {
-      if (delay > 0) std::this_thread::sleep_for(std::chrono::milliseconds(delay));
-      rcs[k] = fixed_msm_one(ctx->devs[k], fb, fb.tab[k], index ? index + lo * t : nullptr, t, cut, scalar32 + lo * t * 32, cnt,
-                             enc32_out + lo * 32, xyzt_out ? xyzt_out + lo * 16 : nullptr);
-      if (rcs[k] != D377_OK) errs[k] = d377_g_err;
-    });
-  }
-  for (auto& w : workers) w.join();
-  for (size_t k = 0; k < nd; ++k)
-    if (rcs[k] != D377_OK) return fail(rcs[k], "%s", errs[k].c_str());
-  return D377_OK;
+  return slice_over_devices(ctx, n, [&](size_t k, size_t lo, size_t cnt) {
+    return fixed_msm_one(ctx->devs[k], fb, fb.tab[k], index ? index + lo * t : nullptr, t, cut, scalar32 + lo * t * 32, cnt,
+                         enc32_out + lo * 32, xyzt_out ? xyzt_out + lo * 16 : nullptr);
+  });
 }
 
 // frees a registration's tables (every device); caller holds ctx->mu or is destroying the context
@@ -390,7 +319,7 @@ int register_bases(d377_ctx* ctx, const char* who, const uint64_t* xyzt, size_t 
   fb->m = m;
   fb->bits = bits;
   fb->tab.assign(ctx->devs.size(), nullptr);
-  int rc = with_width(bits, [&](auto b) -> int {
+  int rc = with_width(bits, WIDTH_REFUSAL, [&](auto b) -> int {
     constexpr int BITS = decltype(b)::value;
     fb->bytes = (uint64_t)(m * comb_bytes<BITS>());
     for (size_t k = 0; k < ctx->devs.size(); ++k) {
@@ -475,7 +404,7 @@ int d377_fixed_bases_destroy(d377_ctx* ctx, int64_t handle) {
   return D377_OK;
 }
 
-// host pointers: contiguous slices of the SUMS over the context's devices, one host thread per device (as batch_msm.hip)
+// host pointers: contiguous slices of the SUMS over the context's devices
 int d377_batch_fixed_msm(d377_ctx* ctx, int64_t handle, const uint8_t* scalar32, size_t n, uint8_t* enc32_out, uint64_t* xyzt_out) {
   if (!ctx) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_msm: ctx is null");
   if (n && (!scalar32 || !enc32_out)) return fail(D377_ERR_ARG, "%s", "d377_batch_fixed_msm: null buffer");

@@ -4,7 +4,10 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <chrono>
 #include <mutex>
+#include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/decaf377_amd.h"
@@ -266,4 +269,36 @@ struct FixedBases {
   uint64_t bytes = 0;                     // table bytes per device
   std::vector<uint32_t*> tab;             // per device of the context, in its order
 };
+}  // namespace d377
+
+namespace d377 {
+// A host-pointer call's n elements in contiguous slices over the context's devices: f(k, lo, cnt) drives elements
+// [lo, lo + cnt) on device k and returns the slice's code.  One device: on the caller's thread.  Several: ceil(n / devices)
+// elements per device, each slice driven by its own host thread -- copies from pageable caller memory block the issuing
+// thread, so a single thread would run the devices one after another -- and every device has drained before this returns,
+// error or not.  -> the first failing device's code, with that worker's thread-local text.  The caller holds ctx->mu.
+template <class F>
+int slice_over_devices(d377_ctx* ctx, size_t n, F&& f) {
+  const size_t nd = ctx->devs.size();
+  if (nd == 1) return f((size_t)0, (size_t)0, n);
+  const size_t per = (n + nd - 1) / nd;
+  std::vector<int> rcs(nd, D377_OK);
+  std::vector<std::string> errs(nd);
+  std::vector<std::thread> workers;
+  const int delay = debug_device_delay_ms();
+  for (size_t k = 0; k < nd; ++k) {
+    const size_t lo = per * k;
+    if (lo >= n) break;
+    const size_t cnt = (lo + per <= n) ? per : n - lo;
+    workers.emplace_back([&, k, lo, cnt]() {
+      if (delay > 0) std::this_thread::sleep_for(std::chrono::milliseconds(delay));
+      rcs[k] = f(k, lo, cnt);
+      if (rcs[k] != D377_OK) errs[k] = d377_g_err;
+    });
+  }
+  for (auto& w : workers) w.join();
+  for (size_t k = 0; k < nd; ++k)
+    if (rcs[k] != D377_OK) return fail(rcs[k], "%s", errs[k].c_str());
+  return D377_OK;
+}
 }  // namespace d377
