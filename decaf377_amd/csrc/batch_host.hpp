@@ -60,11 +60,12 @@ inline int straus_scratch_reserve(DeviceState& d, hipStream_t s, size_t terms, c
   return D377_OK;
 }
 
-// The chunks of a lane-set kernel over `count` elements (deal_chunks): the launch's grid and its DcbScratch.  A launch of at
-// most two generations of workgroups asks for issue priority by progress (dcb.hpp), as d377.hip's chunks_of.
-inline DcbScratch lane_chunks(const DeviceState& d, size_t count, int* grid) {
+// The chunks of a lane-set kernel over `count` elements (deal_chunks), at most kmax rounds per chunk: the launch's grid and
+// its DcbScratch.  A launch of at most two generations of workgroups asks for issue priority by progress (dcb.hpp), as
+// d377.hip's chunks_of.
+inline DcbScratch lane_chunks(const DeviceState& d, size_t count, int* grid, int kmax = DCB_K) {
   const size_t places = (size_t)d.cus * WAVES_PER_SIMD;
-  const ChunkDeal c = deal_chunks((count + BLOCK - 1) / BLOCK, places, (size_t)DCB_K, (size_t)d.cus * 64);
+  const ChunkDeal c = deal_chunks((count + BLOCK - 1) / BLOCK, places, (size_t)kmax, (size_t)d.cus * 64);
   DcbScratch dcb{d.dcb_scratch, d.slot_pool, d.cus * WAVES_PER_SIMD, (int)c.per_lane, d.dcb_sets * BLOCK, (int)c.extra, d.pool_health};
   dcb.prio = c.nchunks <= 2 * places ? 1 : 0;
   *grid = (int)c.nchunks;

@@ -1319,15 +1319,6 @@ size_t tiny_batch_max(const DeviceState& d) {
 size_t tiny4_batch_max(const DeviceState& d) { return tiny_batch_max(d) * TINY4; }
 unsigned tiny4_grid(size_t n) { return (unsigned)((n + TINY4 - 1) / TINY4); }
 
-int grid_for(const DeviceState& d, size_t n) {
-  // >> 256 workgroups when the batch allows it; capped so huge batches grid-stride
-  size_t blocks = (n + BLOCK - 1) / BLOCK;
-  size_t cap = (size_t)d.cus * 32;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
-
 int init_tables(DeviceState& d, uint32_t* keys, int* coll) {
   hipLaunchKernelGGL(k_init_gtab, dim3(6), dim3(BLOCK), 0, d.stream, d.gtab);
   hipLaunchKernelGGL(k_init_slookup, dim3(1), dim3(BLOCK), 0, d.stream, d.s_lookup, keys, coll);
@@ -1568,7 +1559,7 @@ void free_device(DeviceState& d) {
 int launch(DeviceState& d, hipStream_t s, Op op, int aux, const void* in0, const void* in1, size_t n, void* out0, void* out1) {
   if (n == 0) return D377_OK;
   const SqrtTables T = d.tables();
-  const int g = grid_for(d, n);
+  const int g = grid_of(d, n);
   // kernels that work in chunks of DCB_K x 256 elements: one workgroup per chunk (oversubscribed on purpose, see
   // DcbScratch), each claiming one of the vb_blocks resident lane sets of the per-device scratch areas
   // DCB_K elements per lane when the batch is large enough to fill the resident lane sets that way, fewer otherwise

@@ -158,6 +158,15 @@ struct DeviceState {
   SqrtTables tables() const { return SqrtTables{gtab, s_lookup, inv_fail}; }
 };
 
+// Workgroups of BLOCK lanes for n elements: >> 256 workgroups when the batch allows it; capped so huge batches grid-stride
+inline int grid_of(const DeviceState& d, size_t n) {
+  size_t blocks = (n + BLOCK - 1) / BLOCK;
+  size_t cap = (size_t)d.cus * 32;
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  return (int)blocks;
+}
+
 // How a chunked kernel's rounds (of BLOCK elements) are dealt out to its workgroups.  `places` workgroups are resident at a
 // time and a chunk holds at most kmax rounds (elements per lane).  Up to one round per place: a workgroup per round.
 // Otherwise G = the fewest generations of resident workgroups that can hold the rounds: exactly G x places chunks, the rounds

@@ -26,6 +26,11 @@
 //
 // Group-element outputs are canonical as encodings, so the result bytes equal the reference's
 // whatever the summation order (the scatter order is non-deterministic; the sum is not).
+//
+// The host side decides nothing about the bucket method here: msm_plan.hpp's msm_plan turns n, the window width (pick_window),
+// the device's size and the developer overrides into every route, launch shape and workspace region, checked on the CPU
+// (tests/test_msm_plan_host.py).  msm_launch reserves plan.bytes and launches in three phases -- msm_prepare_count (prepare,
+// count), msm_scan_place (scans, the two placement levels), msm_sums (spans, reduction levels, buckets, weighted sums, final).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -44,22 +49,14 @@
 #include "quad_ops.hpp"
 #include "row_ops.hpp"
 #include "host_state.hpp"
+#include "batch_host.hpp"
 
 using namespace d377;
 
 namespace {
 
-constexpr int PT_WORDS = 4 * SLOT;      // one cached or extended point record: 192 B
-constexpr int CHUNK = 8;                // buckets per lane in k_msm_chunks (short chains: this phase is latency-bound)
-constexpr int FOLD = 4;                 // points per lane in k_msm_fold (a serial chain per lane: short chains, more levels)
-// Partial sums per lane in the further reduction levels (k_msm_reduce), level 2, 3, 4, and `skip`: a level runs only if some
-// bucket still has more than this many partials; fewer are summed by the lane (or pair of lanes) that finishes the bucket.
-// With the span sums a bucket of random scalars is left with 1 + size / L partials -- one to three -- so no level runs; the
-// levels are for runs that hold most of the points (many equal scalars: one bucket with thousands of partials), which each
-// level cuts by its group size.  (Rounds 3-4, one lane per <= seg points of a bucket: 4-30 partials per bucket, skip and
-// the segment length swept at 2^16 ... 2^22, everything within 2 %.)
-struct RedSizes { int g[3]; uint32_t skip; };
-constexpr RedSizes RED_DEFAULT = {{8, 8, 32}, 32};
+// the sizes msm_plan.hpp restates from the device-only headers
+static_assert(PLAN_BLOCK == BLOCK && PLAN_AP_WORDS == AP_WORDS && PLAN_RQ_WORDS == row::RQ_WORDS && PT_WORDS == 4 * SLOT, "msm_plan.hpp");
 
 // Every input point is normalised to affine form once (Z = 1 already after decompression; one batched inversion
 // per lane for Element inputs) and stored as a cached AFFINE record (device_util.hpp: pt_store_affine, 128 bytes,
@@ -314,18 +311,7 @@ __global__ void __launch_bounds__(SORT_THREADS) k_msm_count(const DT* digits, si
 // k_msm_scan1: sizes, their prefix local to 1024 buckets, chunk totals; k_msm_scan2: the final offs, L from the total
 // number of entries, the plan (partials per bucket, groups per level, the levels' maxima) with chunk-local prefixes;
 // k_msm_scan3: adds the chunk carries and writes the per-window bases.
-constexpr int REDUCE_LEVELS = 4;
-// lvlmax (zeroed by the host before the launch) receives, per reduction level l and WINDOW w, the largest number of
-// level-(l+1) partials any bucket of that window has -- lvlmax[l * LVL_STRIDE + w] -- and per level the largest over all
-// windows, lvlmax[REDUCE_LEVELS * LVL_STRIDE + l].  A level returns at once when no window needs it, and leaves the
-// windows alone whose buckets are down to `skip` partials: the lane that finishes the bucket adds those (k_msm_buckets).
-constexpr int LVL_STRIDE = 64;
-constexpr int LVL_WORDS = REDUCE_LEVELS * LVL_STRIDE + REDUCE_LEVELS;
-constexpr int SEG_BLOCKS_PER_CU = 4;             // workgroups of k_msm_spans per CU (128 VGPRs: tests/test_codegen.py)
-constexpr uint32_t SPAN_MIN = 8;                 // entries per lane at least (a lane's locate + store are worth ~1 addition)
-// the plan's scalars: [0] L, [1] entries of all windows, [2] lanes of all windows
-constexpr int META_WORDS = 4;
-struct WinInfo { uint32_t len, lane0, ne0, lanes; };     // per window; entry [W] holds the totals in lane0 / ne0
+// (REDUCE_LEVELS, the layout of lvlmax, SPAN_MIN, the meta words and WinInfo: msm_plan.hpp)
 __global__ void __launch_bounds__(1024) k_msm_scan1(uint32_t* blockhist, uint32_t* offs, uint32_t* bsz, uint32_t* tot, int nb, int S,
                                                     int nchunk) {
   __shared__ uint32_t part[1024];
@@ -379,9 +365,7 @@ __global__ void __launch_bounds__(1024) k_msm_scan2(uint32_t* offs, const uint32
   __syncthreads();
   const uint32_t E = s_E;
   // one generation: L = entries / lanes the kernel keeps resident (a window's last lane is part full: W lanes spare)
-  uint32_t L = forced_L ? forced_L : (E + lanes_target - 1) / lanes_target;
-  if (L < SPAN_MIN && !forced_L) L = SPAN_MIN;
-  if (L < 1) L = 1;
+  const uint32_t L = span_len(E, lanes_target, forced_L);
   if (blockIdx.x == 0 && t == 0) { meta[0] = L; meta[1] = E; }
   uint32_t start = 0, size = 0;
   if (j < len) {
@@ -458,7 +442,6 @@ __global__ void __launch_bounds__(1024) k_msm_scan3(const uint32_t* offs, uint32
 // that consecutive threads store to consecutive addresses (runs of ~TILE / bins entries): a wave store that touches
 // 64 different lines costs the address coalescer 64 cycles, and three of those per entry were what was left of the
 // sort (1.36 ms at 2^22) once the lines stayed in cache.
-constexpr int SUPER_BITS = 7, SUPER = 1 << SUPER_BITS;
 constexpr int MSM_MAX_WINDOW = 18;                                     // widest window: digits as int32 beyond 16 bits
 constexpr int MAX_SUPER = ((1 << (MSM_MAX_WINDOW - 1)) + 1 + SUPER - 1) / SUPER;   // 1 025 super-buckets at 18 bits
 constexpr int MAX_BINS = MAX_SUPER > SUPER ? MAX_SUPER : SUPER;
@@ -587,10 +570,7 @@ __device__ __forceinline__ void tile_scatter(TileLds& L, size_t lo, size_t hi, i
   }
 }
 
-// PACKED (batches of up to 2^24 points): the level-1 entry is ONE word -- sign, the 7 bits of the bucket within its
-// super-bucket, 24 bits of point index -- instead of a word and a byte in two arrays (the byte stores came in runs of a few
-// dozen bytes: 5 bytes written and 5 read per entry became 4 and 4).
-constexpr size_t PACKED_MAX_POINTS = (size_t)1 << 24;
+// (PACKED, batches of up to PACKED_MAX_POINTS points: the level-1 entry is ONE word, msm_plan.hpp)
 // (TileLds is 73 KiB with bins for 18-bit windows: beyond the 64 KiB of static LDS, so both levels take it as dynamic LDS)
 template <bool PACKED, class DT>
 __global__ void __launch_bounds__(SORT_THREADS) k_msm_place1(const DT* digits, size_t n, int nb, int S, size_t per,
@@ -960,11 +940,8 @@ k_msm_fold(const uint32_t* in, int W, int m, int mout, uint32_t* out) {
 // The tree's LEAVES are the buckets 1 .. 2^(c-1), numbered from 0 (bucket 0 is always empty: digit 0 places nothing), so
 // the tree is c - 1 levels deep, a whole number of blocks, and S_w = sum_i (i + 1) L_i = sum_j 2^j V_j + T.  (Numbered
 // by bucket index it was 2^(c-1) + 1 leaves: a level, a Horner step and a block per window for the one top bucket.)
-constexpr int WS_M = 8;                          // 2^WS_M buckets per workgroup of k_msm_wsum_block / block2
-constexpr int WS_M8 = 9;                         // 2^WS_M8 per workgroup of k_msm_wsum_block8 (eight buckets per lane)
-constexpr int NODE_STRIDE = WS_M8 + 1;           // points per block node in global memory (a node of depth m uses m + 1)
+// (WS_M, WS_M8, NODE_STRIDE, LP_WORDS: msm_plan.hpp)
 constexpr int WS_THREADS = 1 << (WS_M - 2);      // one wave: a lane takes FOUR buckets through levels 0 and 1 in registers
-constexpr int LP_WORDS = 4 * NL;
 struct LdsPts {
   uint32_t* base;
   int cap;                                       // word k of point p lives at base[k * cap + p]
@@ -1164,22 +1141,12 @@ k_msm_wsum_block8(const uint32_t* buckets, int nb, int m, int nblk, uint32_t* no
 // The block nodes of one window -> S_w.  Levels m .. c-1 (none when one block covers the window), then Horner over the
 // bit-sums with the cooperative doubling / addition of the tail below.
 constexpr int WSB_THREADS = 512;
-// The two point buffers of k_msm_wsum_window (dynamic LDS): the level that merges the block nodes leaves 2^(depth-m-1) nodes
-// of m + 2 points, the next half as many of m + 3, and from there the levels shrink; the second buffer also carries the
-// depth + 1 row records of the Horner chain.  Depth 13 (14-bit windows): 160 + 88 points, 35 KB; depth 15 (16-bit): 640 + 352, 140 KB.
-inline int wsb_cap0(int depth, int m) { return depth > m ? (1 << (depth - m - 1)) * (m + 2) : m + 1; }
-inline int wsb_cap1(int depth, int m) {
-  int pts = depth > m + 1 ? (1 << (depth - m - 2)) * (m + 3) : 0;
-  const int rec = ((depth + 1) * RQ_WORDS + LP_WORDS - 1) / LP_WORDS;       // the Horner chain's records, in points
-  return pts > rec ? pts : rec;
-}
+// (its two point buffers in dynamic LDS, wsb_cap0 / wsb_cap1: msm_plan.hpp)
 // The levels between the block nodes and k_msm_wsum_window for trees deeper than 16 (windows of 17 and 18 bits: 2^16 or 2^17
 // leaves, 128 or 256 block nodes per window -- k_msm_wsum_window's first merged level alone would be 200 KB of LDS): workgroup
 // (window, group) merges 2^(m_out - m_in) consecutive block nodes of depth m_in into one node of depth m_out (m_out + 1
 // points), first level from global memory, the rest in LDS.
 constexpr int WSM_THREADS = 256;
-constexpr int MID_STRIDE = 16;                   // points per node of the middle level (depth <= 15)
-constexpr int WSM_CAP = 96;                      // points per LDS buffer: 8 nodes of 11 points after the first level of a 16-to-1 merge
 __global__ void __launch_bounds__(WSM_THREADS)
 k_msm_wsum_mid(const uint32_t* nodes_in, int m_in, int nblk_in, int m_out, int nblk_out, uint32_t* nodes_out) {
   __shared__ uint32_t lds[2 * WSM_CAP * LP_WORDS];
@@ -1520,8 +1487,6 @@ k_msm_combine(SqrtTables T, const uint64_t* xyzt, size_t m, uint8_t* enc_out, ui
 }
 
 // ------------------------------------------------------------------------------ host side ---
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // Window width.  Only widths that tile the 252 scalar bits exactly are chosen (12, 14; the override also takes others):
 // then the top window is as wide as the others and, because scalars are < r < 2^251, its unsigned
 // digits spread over the same 2^(c-1) buckets as the signed digits of the other windows.  A ragged
@@ -1546,17 +1511,6 @@ int pick_window(const DeviceState& d, size_t n) {
   // (profiles/r06_msm_breakdown_16_17_18.txt).  They stay behind the override for batches beyond 2^24.
   const int c = n >= ((size_t)3 << 20) ? 16 : (n >= ((size_t)1 << 19) ? 14 : 12);
   return (int)d.tuned(D377_TUNE_MSM_WINDOW, c);              // developer override: 4 .. 18 (>= 4: at most 63 windows, k_msm_final's table of cached sums)
-}
-
-// Lanes of the span sums (k_msm_spans): as many as the device keeps resident at once -- what the runtime says the kernel's
-// registers allow (4 workgroups per CU at 128 VGPRs: tests/test_codegen.py) -- less one per window (a window's last lane
-// is part full).  k_msm_scan2 turns it into L = entries / lanes on the device, where the entries are known.
-int grid_of(const DeviceState& d, size_t n) {
-  size_t blocks = (n + BLOCK - 1) / BLOCK;
-  size_t cap = (size_t)d.cus * 32;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
 }
 
 // The workspace: grown when a call needs more (never inside a stream capture), handed from stream to stream by its guard.
@@ -1626,250 +1580,179 @@ int msm_launch_small(DeviceState& d, hipStream_t s, bool encoded, const void* pt
   return held.finish();
 }
 
+// ---- the bucket method's launcher: msm_plan.hpp decides every route, size and offset; the three phases below launch ----------
+struct MsmCall { DeviceState& d; hipStream_t s; const MsmPlan& p; size_t n; };
+// region r of the workspace
+template <class T = uint32_t>
+T* msm_at(const MsmCall& c, MsmRegion r) { return reinterpret_cast<T*>(c.d.msm.mem + c.p.region[r].offset); }
+
+// Phase 1: prepare (points -> affine records, scalars -> digits) and the counting pass, for the digit type of this window width
+template <class DT>
+int msm_prepare_count(const MsmCall& c, bool encoded, const void* pts_in, const uint8_t* scalars, uint8_t* status) {
+  DeviceState& d = c.d; const MsmPlan& p = c.p; const hipStream_t s = c.s; const size_t n = c.n;
+  const SqrtTables T = d.tables();
+  uint32_t* pts = msm_at(c, R_PTS);
+  DT* dig = msm_at<DT>(c, R_DIGITS);
+  if (p.hist_bytes > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_count<DT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.hist_bytes));
+  if (n) {
+    if (encoded) {
+      const size_t chunked_min = (size_t)d.tuned(D377_TUNE_MSM_ENC_CHUNKED_MIN, (long long)(d.resident_lanes() * DCB_ASSIST_MIN));
+      if (n >= chunked_min && d.msm_enc_chunked < 0) {
+        // the chunked kernel claims lane sets of the scratch areas: only if its residency matches them (as d377_ctx_create
+        // checks for the kernels of d377.hip); otherwise the wide kernel stays
+        int nbk = 0, nbk32 = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, reinterpret_cast<const void*>(k_msm_prepare_enc_chunked<int16_t>), BLOCK, 0));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk32, reinterpret_cast<const void*>(k_msm_prepare_enc_chunked<int32_t>), BLOCK, 0));
+        d.msm_enc_chunked = (nbk >= 1 && nbk <= WAVES_PER_SIMD && nbk32 >= 1 && nbk32 <= WAVES_PER_SIMD) ? 1 : 0;
+      }
+      if (n >= chunked_min && d.msm_enc_chunked == 1) {
+        int grid;
+        const DcbScratch dcb = lane_chunks(d, n, &grid, DCB_K_LONG);
+        GuardScope vb{d.vb_guard, s};                       // the lane-set areas: queue behind their last user
+        int r;
+        if ((r = vb.acquire())) return r;
+        hipLaunchKernelGGL(k_msm_prepare_enc_chunked<DT>, dim3((unsigned)grid), dim3(BLOCK), 0, s, T, (const uint8_t*)pts_in, scalars, n, p.shape,
+                           pts, dig, status, dcb);
+        if ((r = vb.finish())) return r;
+      } else {
+        hipLaunchKernelGGL(k_msm_prepare_enc<DT>, dim3(grid_of(d, n)), dim3(BLOCK), 0, s, T, (const uint8_t*)pts_in, scalars, n, p.shape, pts,
+                           dig, status);
+      }
+    } else {
+      uint32_t* zflag = msm_at(c, R_FLAG);
+      HIP_TRY(hipMemsetAsync(zflag, 0, sizeof(uint32_t), s));
+      hipLaunchKernelGGL(k_msm_prepare_affine<DT>, dim3(grid_of(d, n)), dim3(BLOCK), 0, s, T, (const uint64_t*)pts_in, scalars, n, p.shape, pts,
+                         dig, zflag);
+      // ~32 elements per lane share one inversion, but never fewer lanes than one wave per SIMD (see k_to_affine)
+      size_t lanes = (n + 31) / 32;
+      const size_t fill = (size_t)d.cus * BLOCK;
+      if (lanes < fill) lanes = fill < n ? fill : n;
+      hipLaunchKernelGGL(k_msm_prepare_el<DT>, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, (const uint64_t*)pts_in,
+                         scalars, n, p.shape, pts, dig, zflag);
+    }
+  }
+  hipLaunchKernelGGL(k_msm_count<DT>, dim3(p.W * p.S * p.count_parts), dim3(SORT_THREADS), p.hist_bytes, s, dig, n, p.nb, p.S, p.per, p.count_parts,
+                     p.count_nbr, msm_at(c, R_BLOCKHIST));
+  return D377_OK;
+}
+
+// Phase 2: the scans (bucket offsets, L, the plan of the bucket sums) and the two placement levels of the sort (TileLds: 73 KiB
+// of dynamic LDS each).  Level 1 writes R_TMP_IDX, the view of R_PARTIALS that is free until k_msm_spans.
+template <bool PK, class DT>
+int msm_place(const MsmCall& c) {
+  const MsmPlan& p = c.p;
+  const size_t tile_lds = sizeof(TileLds);
+  uint32_t *tmp_idx = msm_at(c, R_TMP_IDX), *offs = msm_at(c, R_OFFS);
+  uint8_t* tmp_sub = msm_at<uint8_t>(c, R_SUB);
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_place1<PK, DT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_place2<PK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
+  hipLaunchKernelGGL((k_msm_place1<PK, DT>), dim3(p.W * p.S), dim3(SORT_THREADS), tile_lds, c.s, msm_at<const DT>(c, R_DIGITS), c.n, p.nb, p.S, p.per,
+                     msm_at(c, R_BLOCKHIST), offs, tmp_idx, tmp_sub);
+  hipLaunchKernelGGL(k_msm_place2<PK>, dim3(p.W * ((p.nb + SUPER - 1) / SUPER)), dim3(SORT_THREADS), tile_lds, c.s, tmp_idx, tmp_sub, c.n, p.nb, offs,
+                     msm_at(c, R_IDX));
+  return D377_OK;
+}
+int msm_scan_place(const MsmCall& c) {
+  const MsmPlan& p = c.p; const hipStream_t s = c.s;
+  uint32_t *offs = msm_at(c, R_OFFS), *segoff = msm_at(c, R_SEGOFF), *bsz = msm_at(c, R_BSZ), *tot = msm_at(c, R_TOT), *tot2 = msm_at(c, R_TOT2);
+  uint32_t *lvlmax = msm_at(c, R_LVLMAX), *meta = msm_at(c, R_META);
+  HIP_TRY(hipMemsetAsync(lvlmax, 0, LVL_WORDS * sizeof(uint32_t), s));
+  const dim3 grid(p.W * p.scan_chunks);
+  hipLaunchKernelGGL(k_msm_scan1, grid, dim3(1024), 0, s, msm_at(c, R_BLOCKHIST), offs, bsz, tot, p.nb, p.S, p.scan_chunks);
+  hipLaunchKernelGGL(k_msm_scan2, grid, dim3(1024), 0, s, offs, bsz, segoff, tot, tot2, p.nb, p.W, p.scan_chunks, p.lanes_target, p.forced_L, p.red,
+                     lvlmax, meta);
+  hipLaunchKernelGGL(k_msm_scan3, grid, dim3(1024), 0, s, offs, segoff, tot2, p.nb, p.W, p.scan_chunks, meta, msm_at<WinInfo>(c, R_WINFO));
+  if (p.wide_digits) return p.packed ? msm_place<true, int32_t>(c) : msm_place<false, int32_t>(c);
+  return p.packed ? msm_place<true, int16_t>(c) : msm_place<false, int16_t>(c);
+}
+
+// Phase 3: the span sums, the reduction levels, the buckets, the weighted sums per window and the final Horner chain
+int msm_sums(const MsmCall& c, uint8_t* enc_out, uint64_t* xyzt_out) {
+  DeviceState& d = c.d; const MsmPlan& p = c.p; const hipStream_t s = c.s;
+  const int W = p.W, nb = p.nb;
+  uint32_t *segoff = msm_at(c, R_SEGOFF), *lvlmax = msm_at(c, R_LVLMAX), *meta = msm_at(c, R_META), *bkt = msm_at(c, R_BUCKETS);
+  const SpanPlan sp{msm_at(c, R_OFFS), segoff, msm_at<WinInfo>(c, R_WINFO), 0u};      // (L travels in meta: the kernels read it there)
+  uint32_t* partial = msm_at(c, R_PARTIALS);
+  hipLaunchKernelGGL(k_msm_spans, dim3(grid_of(d, p.span_lanes_max)), dim3(BLOCK), 0, s, msm_at(c, R_PTS), msm_at(c, R_IDX), sp, meta, c.n, W, nb,
+                     partial);
+  const size_t so_stride = (size_t)W * (nb + 1);
+  MsmLevels lv;
+  lv.buf[0] = partial;
+  for (int l = 1; l < REDUCE_LEVELS; ++l) {
+    uint32_t* r = msm_at(c, (MsmRegion)(R_RED1 + l - 1));
+    // (the levels only ever run for runs that hold most of the points: a small grid that strides, so that the launch that
+    // finds nothing to do costs a few hundred workgroups, not thousands)
+    int gr = grid_of(d, p.max_g[l]);
+    if (gr > d.cus * 4) gr = d.cus * 4;
+    hipLaunchKernelGGL(k_msm_reduce, dim3(gr), dim3(BLOCK), 0, s, lv.buf[l - 1], sp, segoff + (size_t)(l - 1) * so_stride,
+                       segoff + (size_t)l * so_stride, W, nb, p.max_g[l], r, p.red.g[l - 1], lvlmax, l - 1, p.red.skip, meta);
+    lv.buf[l] = r;
+  }
+  if (p.bucket_lanes == 1)
+    hipLaunchKernelGGL(k_msm_buckets<1>, dim3(grid_of(d, (size_t)W * nb)), dim3(BLOCK), 0, s, lv, sp, segoff, lvlmax, p.red.skip, W, nb, bkt, meta);
+  else
+    hipLaunchKernelGGL(k_msm_buckets<2>, dim3(grid_of(d, (size_t)W * nb * 2)), dim3(BLOCK), 0, s, lv, sp, segoff, lvlmax, p.red.skip, W, nb, bkt, meta);
+  const uint32_t* cur_in;
+  if (p.tree) {
+    uint32_t *nodes = msm_at(c, R_NODES), *sums = msm_at(c, R_SUMS);
+    const dim3 blocks(W * p.ws_nblk);
+    if (p.block_kernel == WSUM_BLOCK8) hipLaunchKernelGGL(k_msm_wsum_block8, blocks, dim3(WS8_THREADS), 0, s, bkt, nb, p.ws_m, p.ws_nblk, nodes);
+    else if (p.block_kernel == WSUM_BLOCK2) hipLaunchKernelGGL(k_msm_wsum_block2, blocks, dim3(WS2_THREADS), 0, s, bkt, nb, p.ws_m, p.ws_nblk, nodes);
+    else hipLaunchKernelGGL(k_msm_wsum_block, blocks, dim3(WS_THREADS), 0, s, bkt, nb, p.ws_m, p.ws_nblk, nodes);
+    const uint32_t* top_nodes = nodes;
+    if (p.ws_mid) {
+      uint32_t* mid = msm_at(c, R_MID);
+      hipLaunchKernelGGL(k_msm_wsum_mid, dim3(W * p.mid_nblk), dim3(WSM_THREADS), 0, s, nodes, p.ws_m, p.ws_nblk, p.mid_m, p.mid_nblk, mid);
+      top_nodes = mid;
+    }
+    if (p.wsb_lds > 64 * 1024)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_wsum_window), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.wsb_lds));
+    hipLaunchKernelGGL(k_msm_wsum_window, dim3(W), dim3(WSB_THREADS), p.wsb_lds, s, top_nodes, p.ws_depth, p.top_m, p.top_nblk, p.top_stride, p.cap0,
+                       p.cap1, sums);
+    cur_in = sums;
+  } else {
+    uint32_t* ch = msm_at(c, R_CHUNKS);
+    hipLaunchKernelGGL(k_msm_chunks, dim3(grid_of(d, (size_t)W * p.nchunks)), dim3(BLOCK), 0, s, bkt, W, nb, p.nchunks, ch);
+    cur_in = ch;
+    for (int f = 0; f < p.nfolds; ++f) {                       // fold the chunk results down to one point per window
+      const MsmFoldStep& st = p.fold[f];
+      uint32_t* o = msm_at(c, (MsmRegion)(R_FOLD0 + st.buf));
+      hipLaunchKernelGGL(k_msm_fold, dim3(grid_of(d, (size_t)W * st.m_out)), dim3(BLOCK), 0, s, cur_in, W, st.m_in, st.m_out, o);
+      cur_in = o;
+    }
+  }
+  hipLaunchKernelGGL(k_msm_final, dim3(1), dim3(64), 0, s, d.tables(), cur_in, p.shape, enc_out, xyzt_out);
+  return D377_OK;
+}
+
 // everything on device pointers, enqueued on `s`
 int msm_launch(DeviceState& d, hipStream_t s, bool encoded, const void* pts_in, const uint8_t* scalars, size_t n,
                uint8_t* enc_out, uint64_t* xyzt_out, uint8_t* status) {
   if (n >= ((size_t)1 << 31)) return fail(D377_ERR_ARG, "%s", "msm: n must be below 2^31");
   if (n && n <= msm_small_max(d, encoded) && n < ((size_t)1 << 24)) return msm_launch_small(d, s, encoded, pts_in, scalars, n, enc_out, xyzt_out, status);
-  const int c = pick_window(d, n);
-  const WinShape wshape = win_shape(c);                      // W windows of c or c - 1 bits that tile the 252 scalar bits
-  const int W = wshape.W;
-  const int nb = (1 << (c - 1)) + 1;                         // bucket indices 0 .. 2^(c-1)
-  const int nchunks = (nb - 1 + CHUNK - 1) / CHUNK;
-  // workspace carve-up
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-  // slices per window of the counting sort: enough workgroups to cover the chip, never less than 8192 points each
-  // (W * S <= the 2 workgroups of 1024 threads a CU holds: with one more slice per window, 18 x 29 = 522 workgroups on 512
-  // places, the count and level-1 placement kernels ran a second generation for ten workgroups)
-  int S = (int)d.tuned(D377_TUNE_MSM_SLICES, (long long)((size_t)2 * d.cus / (size_t)W));   // developer override (sweeps): 1 .. 4096
-  if ((size_t)S > (n + 8191) / 8192) S = (int)((n + 8191) / 8192);
-  if (S < 1) S = 1;
-  const size_t per = (n + (size_t)S - 1) / (size_t)S;
-  const size_t o_flag = carve(256);
-  const size_t o_pts = carve(n * AP_WORDS * 4);
-  const bool wide_digits = c > 16;                            // |digit| <= 2^(c-1): int16 up to 16-bit windows, int32 beyond
-  const size_t o_dig = carve((size_t)W * n * (wide_digits ? 4 : 2));
-  const size_t o_bh = carve((size_t)W * S * nb * 4);
-  const size_t o_off = carve((size_t)W * (nb + 1) * 4);
-  const size_t o_seg = carve((size_t)REDUCE_LEVELS * W * (nb + 1) * 4);
-  const size_t o_bsz = carve((size_t)W * (nb + 1) * 4);
-  const int scan_chunks = (nb + 1 + 1023) / 1024;
-  const size_t o_tot = carve((size_t)W * scan_chunks * 4);
-  const size_t o_tot2 = carve((size_t)W * scan_chunks * REDUCE_LEVELS * 4);
-  const size_t o_meta = carve(META_WORDS * sizeof(uint32_t));
-  const size_t o_winfo = carve((size_t)(W + 1) * sizeof(WinInfo));
-  // the span sums: lanes resident at once (asked once per device), entries per lane when a developer forces them
+  MsmPlanIn in;
+  in.n = n; in.c = pick_window(d, n); in.cus = d.cus;
+  // Lanes of the span sums (k_msm_spans): as many as the device keeps resident at once -- what the runtime says the kernel's
+  // registers allow (4 workgroups per CU at 128 VGPRs: tests/test_codegen.py), asked once per device.
   if (d.msm_span_blocks < 0) {
     int nblk = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, reinterpret_cast<const void*>(k_msm_spans), BLOCK, 0));
     d.msm_span_blocks = nblk < 1 ? 1 : (nblk > SEG_BLOCKS_PER_CU ? SEG_BLOCKS_PER_CU : nblk);
   }
-  const size_t span_resident = (size_t)d.cus * d.msm_span_blocks * BLOCK;
-  const uint32_t lanes_target = (uint32_t)(span_resident - (size_t)W);
-  const uint32_t forced_L = (uint32_t)d.tuned(D377_TUNE_MSM_SEG, 0);             // developer override: entries per span lane
-  // partial slots: one per lane and one per non-empty bucket (a lane stores one partial per bucket its span touches)
-  const size_t span_lanes_max = forced_L ? ((size_t)n * W) / forced_L + (size_t)W + 1 : (((size_t)n * W) / SPAN_MIN + (size_t)W + 1 < span_resident
-                                                                                          ? ((size_t)n * W) / SPAN_MIN + (size_t)W + 1 : span_resident);
-  const size_t max_segs = span_lanes_max + (size_t)W * nb + 1;
-  // the level-1 index array of the sort (W * n words) borrows the span partials' area, which is free until k_msm_spans
-  const size_t par_bytes = max_segs * PT_WORDS * 4, tmp_bytes = (size_t)W * n * 4;
-  const size_t o_par = carve(par_bytes > tmp_bytes ? par_bytes : tmp_bytes);
-  const size_t o_idx = carve((size_t)W * n * 4);
-  const size_t o_sub = carve((size_t)W * n);                            // level-1 placement: bucket index within the super-bucket
-  const size_t o_bkt = carve((size_t)W * nb * PT_WORDS * 4);
-  // further levels of the bucket reduction: groups of partials, then groups of those (never more than this many); every
-  // level is launched and decides on the device whether it has anything to do (k_msm_scan1, lvlmax)
-  RedSizes red = RED_DEFAULT;
-  red.g[0] = (int)d.tuned(D377_TUNE_MSM_RED, red.g[0]);       // developer overrides (sweeps): 2 .. 64, 1 .. 64
-  red.skip = (uint32_t)d.tuned(D377_TUNE_MSM_SKIP, red.skip);
-  size_t max_g[REDUCE_LEVELS];
-  size_t o_r[REDUCE_LEVELS];
-  max_g[0] = max_segs; o_r[0] = o_par;
-  for (int l = 1; l < REDUCE_LEVELS; ++l) {
-    max_g[l] = max_g[l - 1] / (size_t)red.g[l - 1] + (size_t)W * nb;
-    o_r[l] = carve(max_g[l] * PT_WORDS * 4);
-  }
-  const size_t o_lvl = carve(LVL_WORDS * sizeof(uint32_t));
-  const size_t o_ch = carve((size_t)W * nchunks * PT_WORDS * 4);
-  // ping-pong buffers of the 32-to-1 folds, sized from the fold sequence itself: the first fold writes
-  // ceil(nchunks / FOLD) records per window into f0, the second ceil(that / FOLD) into f1, and so on
-  const size_t m1 = (size_t)(nchunks + FOLD - 1) / FOLD, m2 = (m1 + FOLD - 1) / FOLD;
-  const size_t o_f0 = carve((size_t)W * m1 * PT_WORDS * 4);
-  const size_t o_f1 = carve((size_t)W * m2 * PT_WORDS * 4);
-  // weighted bucket sums by the pairwise tree (every width: c <= 16); the chunked running sums remain as a developer
-  // override (D377_TUNE_MSM_CHUNKED_SUMS), the tree's cross-check
-  const bool tree = d.tuned(D377_TUNE_MSM_CHUNKED_SUMS, 0) == 0;
-  // the tree's leaves are buckets 1 .. 2^(c-1) (bucket 0 is empty): depth c - 1, a whole number of blocks
-  const int ws_depth = c - 1;
-  // 512 leaves per workgroup (k_msm_wsum_block8) where 256 per workgroup would not fit the chip at once: three of those per CU
-  const bool ws8 = ws_depth >= WS_M8 && (size_t)W * ((size_t)1 << (ws_depth - WS_M)) > (size_t)d.cus * 3;
-  const int ws_m = ws8 ? WS_M8 : (ws_depth < WS_M ? ws_depth : WS_M);        // >= 2: window widths start at 4 here
-  const int ws_nblk = 1 << (ws_depth - ws_m);
-  const size_t o_nodes = carve(tree ? (size_t)W * ws_nblk * NODE_STRIDE * PT_WORDS * 4 : 0);
-  // trees deeper than 15 (17- and 18-bit windows): a middle level merges the block nodes 8 or 16 to 1 (k_msm_wsum_mid), down
-  // to 16 nodes per window for k_msm_wsum_window
-  const bool ws_mid = tree && ws_depth > 15;
-  const int ws_mid_m = ws_depth - 4, ws_mid_nblk = 16;
-  const size_t o_mid = carve(ws_mid ? (size_t)W * ws_mid_nblk * MID_STRIDE * PT_WORDS * 4 : 0);
-  const size_t o_sums = carve((size_t)W * PT_WORDS * 4);
+  in.span_blocks = d.msm_span_blocks;
+  in.slices = d.tuned(D377_TUNE_MSM_SLICES, PLAN_DEFAULT); in.seg = d.tuned(D377_TUNE_MSM_SEG, PLAN_DEFAULT);   // developer overrides (sweeps)
+  in.red = d.tuned(D377_TUNE_MSM_RED, PLAN_DEFAULT); in.skip = d.tuned(D377_TUNE_MSM_SKIP, PLAN_DEFAULT);
+  in.chunked_sums = d.tuned(D377_TUNE_MSM_CHUNKED_SUMS, PLAN_DEFAULT); in.sort_packed = d.tuned(D377_TUNE_MSM_SORT_PACKED, PLAN_DEFAULT);
+  const MsmPlan p = msm_plan(in);
   int rc;
   MsmHeld held{d.msm.guard, s, false};
-  if ((rc = msm_reserve(d, s, off, held))) return rc;
-  uint8_t* m = d.msm.mem;
-  uint32_t* pts = (uint32_t*)(m + o_pts);
-  void* dig_raw = m + o_dig;
-  uint32_t *bh = (uint32_t*)(m + o_bh), *offs = (uint32_t*)(m + o_off);
-  uint32_t *segoff = (uint32_t*)(m + o_seg), *partial = (uint32_t*)(m + o_par);
-  uint32_t* idx = (uint32_t*)(m + o_idx);
-  uint32_t* tmp_idx = partial;                                // free until k_msm_spans writes it
-  uint8_t* tmp_sub = m + o_sub;
-  uint32_t *bkt = (uint32_t*)(m + o_bkt), *ch = (uint32_t*)(m + o_ch), *f0 = (uint32_t*)(m + o_f0), *f1 = (uint32_t*)(m + o_f1);
-  const SqrtTables T = d.tables();
-  // the counting pass keeps a histogram of at most 2^15 + 1 buckets in LDS (128 KiB): wider windows are counted in R parts
-  const int count_parts = (nb + (1 << 15)) / ((1 << 15) + 1);
-  const int count_nbr = (nb + count_parts - 1) / count_parts;
-  const size_t hist_bytes = (size_t)count_nbr * 4;
-  // prepare (points -> affine records, scalars -> digits) and the counting pass, for the digit type of this window width
-  auto front = [&](auto tag) -> int {
-    using DT = decltype(tag);
-    DT* dig = reinterpret_cast<DT*>(dig_raw);
-    if (hist_bytes > 64 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_count<DT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
-    if (n) {
-      if (encoded) {
-        const size_t chunked_min = (size_t)d.tuned(D377_TUNE_MSM_ENC_CHUNKED_MIN, (long long)(d.resident_lanes() * DCB_ASSIST_MIN));
-        if (n >= chunked_min && d.msm_enc_chunked < 0) {
-          // the chunked kernel claims lane sets of the scratch areas: only if its residency matches them (as d377_ctx_create
-          // checks for the kernels of d377.hip); otherwise the wide kernel stays
-          int nbk = 0, nbk32 = 0;
-          HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, reinterpret_cast<const void*>(k_msm_prepare_enc_chunked<int16_t>), BLOCK, 0));
-          HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk32, reinterpret_cast<const void*>(k_msm_prepare_enc_chunked<int32_t>), BLOCK, 0));
-          d.msm_enc_chunked = (nbk >= 1 && nbk <= WAVES_PER_SIMD && nbk32 >= 1 && nbk32 <= WAVES_PER_SIMD) ? 1 : 0;
-        }
-        if (n >= chunked_min && d.msm_enc_chunked == 1) {
-          const ChunkDeal cd = deal_chunks((n + BLOCK - 1) / BLOCK, (size_t)d.cus * WAVES_PER_SIMD, (size_t)DCB_K_LONG, (size_t)d.cus * 64);
-          const size_t nchunks = cd.nchunks;
-          DcbScratch dcb{d.dcb_scratch, d.slot_pool, d.cus * WAVES_PER_SIMD, (int)cd.per_lane, d.dcb_sets * BLOCK, (int)cd.extra, d.pool_health};
-          dcb.prio = nchunks <= 2 * (size_t)d.cus * WAVES_PER_SIMD ? 1 : 0;      // as d377.hip's chunks_of: launches of one or two generations
-          GuardScope vb{d.vb_guard, s};                       // the lane-set areas: queue behind their last user
-          int r;
-          if ((r = vb.acquire())) return r;
-          hipLaunchKernelGGL(k_msm_prepare_enc_chunked<DT>, dim3((unsigned)nchunks), dim3(BLOCK), 0, s, T, (const uint8_t*)pts_in, scalars, n, wshape,
-                             pts, dig, status, dcb);
-          if ((r = vb.finish())) return r;
-        } else {
-          hipLaunchKernelGGL(k_msm_prepare_enc<DT>, dim3(grid_of(d, n)), dim3(BLOCK), 0, s, T, (const uint8_t*)pts_in, scalars, n, wshape, pts,
-                             dig, status);
-        }
-      } else {
-        uint32_t* zflag = (uint32_t*)(m + o_flag);
-        HIP_TRY(hipMemsetAsync(zflag, 0, sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k_msm_prepare_affine<DT>, dim3(grid_of(d, n)), dim3(BLOCK), 0, s, T, (const uint64_t*)pts_in, scalars, n, wshape, pts,
-                           dig, zflag);
-        // ~32 elements per lane share one inversion, but never fewer lanes than one wave per SIMD (see k_to_affine)
-        size_t lanes = (n + 31) / 32;
-        const size_t fill = (size_t)d.cus * BLOCK;
-        if (lanes < fill) lanes = fill < n ? fill : n;
-        hipLaunchKernelGGL(k_msm_prepare_el<DT>, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, (const uint64_t*)pts_in,
-                           scalars, n, wshape, pts, dig, zflag);
-      }
-    }
-    hipLaunchKernelGGL(k_msm_count<DT>, dim3(W * S * count_parts), dim3(SORT_THREADS), hist_bytes, s, dig, n, nb, S, per, count_parts, count_nbr, bh);
-    return D377_OK;
-  };
-  if ((rc = wide_digits ? front(int32_t{}) : front(int16_t{}))) return rc;
-  uint32_t* tot = (uint32_t*)(m + o_tot);
-  uint32_t* lvlmax = (uint32_t*)(m + o_lvl);
-  HIP_TRY(hipMemsetAsync(lvlmax, 0, LVL_WORDS * sizeof(uint32_t), s));
-  uint32_t *bsz = (uint32_t*)(m + o_bsz), *tot2 = (uint32_t*)(m + o_tot2), *meta = (uint32_t*)(m + o_meta);
-  WinInfo* winfo = (WinInfo*)(m + o_winfo);
-  hipLaunchKernelGGL(k_msm_scan1, dim3(W * scan_chunks), dim3(1024), 0, s, bh, offs, bsz, tot, nb, S, scan_chunks);
-  hipLaunchKernelGGL(k_msm_scan2, dim3(W * scan_chunks), dim3(1024), 0, s, offs, bsz, segoff, tot, tot2, nb, W, scan_chunks, lanes_target,
-                     forced_L, red, lvlmax, meta);
-  hipLaunchKernelGGL(k_msm_scan3, dim3(W * scan_chunks), dim3(1024), 0, s, offs, segoff, tot2, nb, W, scan_chunks, meta, winfo);
-  {
-    // the two placement levels (TileLds: 73 KiB of dynamic LDS each)
-    const bool packed = n <= PACKED_MAX_POINTS && d.tuned(D377_TUNE_MSM_SORT_PACKED, 1) != 0;
-    const size_t tile_lds = sizeof(TileLds);
-    auto place = [&](auto tag, auto packed_tag) -> int {
-      using DT = decltype(tag);
-      constexpr bool PK = decltype(packed_tag)::value;
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_place1<PK, DT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_place2<PK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
-      hipLaunchKernelGGL((k_msm_place1<PK, DT>), dim3(W * S), dim3(SORT_THREADS), tile_lds, s, reinterpret_cast<const DT*>(dig_raw), n, nb, S, per, bh, offs,
-                         tmp_idx, tmp_sub);
-      hipLaunchKernelGGL(k_msm_place2<PK>, dim3(W * ((nb + SUPER - 1) / SUPER)), dim3(SORT_THREADS), tile_lds, s, tmp_idx, tmp_sub, n, nb, offs, idx);
-      return D377_OK;
-    };
-    if (wide_digits) rc = packed ? place(int32_t{}, std::true_type{}) : place(int32_t{}, std::false_type{});
-    else rc = packed ? place(int16_t{}, std::true_type{}) : place(int16_t{}, std::false_type{});
-    if (rc) return rc;
-  }
-  const SpanPlan sp{offs, segoff, winfo, 0u};                  // (L travels in meta: the kernels read it there)
-  hipLaunchKernelGGL(k_msm_spans, dim3(grid_of(d, span_lanes_max)), dim3(BLOCK), 0, s, pts, idx, sp, meta, n, W, nb, partial);
-  const size_t so_stride = (size_t)W * (nb + 1);
-  MsmLevels lv;
-  lv.buf[0] = partial;
-  for (int l = 1; l < REDUCE_LEVELS; ++l) {
-    uint32_t* r = (uint32_t*)(m + o_r[l]);
-    // (the levels only ever run for runs that hold most of the points: a small grid that strides, so that the launch that
-    // finds nothing to do costs a few hundred workgroups, not thousands)
-    int gr = grid_of(d, max_g[l]);
-    if (gr > d.cus * 4) gr = d.cus * 4;
-    hipLaunchKernelGGL(k_msm_reduce, dim3(gr), dim3(BLOCK), 0, s, lv.buf[l - 1], sp, segoff + (size_t)(l - 1) * so_stride,
-                       segoff + (size_t)l * so_stride, W, nb, max_g[l], r, red.g[l - 1], lvlmax, l - 1, red.skip, meta);
-    lv.buf[l] = r;
-  }
-  {
-    // partials a bucket is left with when the scalars are random: 1 + its run / the entries per span lane
-    const double run = (double)n / (double)(nb - 1);
-    double Lest = forced_L ? (double)forced_L : (double)n * W / (double)lanes_target;
-    if (!forced_L && Lest < (double)SPAN_MIN) Lest = (double)SPAN_MIN;
-    if (1.0 + run / Lest <= 4.0)
-      hipLaunchKernelGGL(k_msm_buckets<1>, dim3(grid_of(d, (size_t)W * nb)), dim3(BLOCK), 0, s, lv, sp, segoff, lvlmax, red.skip, W, nb, bkt, meta);
-    else
-      hipLaunchKernelGGL(k_msm_buckets<2>, dim3(grid_of(d, (size_t)W * nb * 2)), dim3(BLOCK), 0, s, lv, sp, segoff, lvlmax, red.skip, W, nb, bkt, meta);
-  }
-  const uint32_t* cur_in;
-  if (tree) {
-    uint32_t *nodes = (uint32_t*)(m + o_nodes), *sums = (uint32_t*)(m + o_sums);
-    if (ws8)
-      hipLaunchKernelGGL(k_msm_wsum_block8, dim3(W * ws_nblk), dim3(WS8_THREADS), 0, s, bkt, nb, ws_m, ws_nblk, nodes);
-    else if ((size_t)2 * W * ws_nblk <= (size_t)d.cus * 4)     // two waves per block still leave every wave its own SIMD
-      hipLaunchKernelGGL(k_msm_wsum_block2, dim3(W * ws_nblk), dim3(WS2_THREADS), 0, s, bkt, nb, ws_m, ws_nblk, nodes);
-    else
-      hipLaunchKernelGGL(k_msm_wsum_block, dim3(W * ws_nblk), dim3(WS_THREADS), 0, s, bkt, nb, ws_m, ws_nblk, nodes);
-    const uint32_t* top_nodes = nodes;
-    int top_m = ws_m, top_nblk = ws_nblk, top_stride = NODE_STRIDE;
-    if (ws_mid) {
-      uint32_t* mid = (uint32_t*)(m + o_mid);
-      hipLaunchKernelGGL(k_msm_wsum_mid, dim3(W * ws_mid_nblk), dim3(WSM_THREADS), 0, s, nodes, ws_m, ws_nblk, ws_mid_m, ws_mid_nblk, mid);
-      top_nodes = mid; top_m = ws_mid_m; top_nblk = ws_mid_nblk; top_stride = MID_STRIDE;
-    }
-    const int cap0 = wsb_cap0(ws_depth, top_m), cap1 = wsb_cap1(ws_depth, top_m);
-    const size_t wsb_lds = (size_t)(cap0 + cap1) * LP_WORDS * sizeof(uint32_t);
-    if (wsb_lds > 64 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_wsum_window), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wsb_lds));
-    hipLaunchKernelGGL(k_msm_wsum_window, dim3(W), dim3(WSB_THREADS), wsb_lds, s, top_nodes, ws_depth, top_m, top_nblk, top_stride, cap0, cap1, sums);
-    cur_in = sums;
-  } else {
-    hipLaunchKernelGGL(k_msm_chunks, dim3(grid_of(d, (size_t)W * nchunks)), dim3(BLOCK), 0, s, bkt, W, nb, nchunks, ch);
-    // fold chunk results down to one point per window
-    cur_in = ch;
-    int mcur = nchunks;
-    uint32_t* bufs[2] = {f0, f1};
-    int which = 0;
-    const size_t fold_cap[2] = {m1, m2};
-    while (mcur > 1) {
-      const int mout = (mcur + FOLD - 1) / FOLD;
-      if ((size_t)mout > fold_cap[which]) return fail(D377_ERR_ARG, "%s", "msm: fold buffer too small (internal)");
-      uint32_t* o = bufs[which];
-      hipLaunchKernelGGL(k_msm_fold, dim3(grid_of(d, (size_t)W * mout)), dim3(BLOCK), 0, s, cur_in, W, mcur, mout, o);
-      cur_in = o; mcur = mout; which ^= 1;
-    }
-  }
-  hipLaunchKernelGGL(k_msm_final, dim3(1), dim3(64), 0, s, T, cur_in, wshape, enc_out, xyzt_out);
+  if ((rc = msm_reserve(d, s, p.bytes, held))) return rc;
+  const MsmCall call{d, s, p, n};
+  if ((rc = p.wide_digits ? msm_prepare_count<int32_t>(call, encoded, pts_in, scalars, status)
+                          : msm_prepare_count<int16_t>(call, encoded, pts_in, scalars, status))) return rc;
+  if ((rc = msm_scan_place(call))) return rc;
+  if ((rc = msm_sums(call, enc_out, xyzt_out))) return rc;
   HIP_TRY(hipGetLastError());
   return held.finish();
 }

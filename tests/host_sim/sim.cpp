@@ -614,6 +614,30 @@ void sim_w4_digits(const uint32_t* k, size_t n, int halve, int* digits) {
 void sim_span_plan(const uint32_t* o, const uint32_t* size, size_t nb, uint32_t L, uint32_t* first_lane, uint32_t* partials) {
   for (size_t b = 0; b < nb; ++b) { first_lane[b] = span_first_lane(o[b], L); partials[b] = span_partials(o[b], size[b], L); }
 }
+uint32_t sim_span_len(uint32_t E, uint32_t lanes_target, uint32_t forced_L) { return span_len(E, lanes_target, forced_L); }
+// msm_plan (msm_plan.hpp) for in = {n, c, cus, span_blocks, slices, seg, red, skip, chunked_sums, sort_packed} (-1 = no override).
+// out: the 40 decisions in the order of tests/golden/msm_plan_parent.json's out_fields (block_kernel: 0 block8, 1 block2,
+// 2 block; "ws8" = block8 chosen), then partials_bytes, tmp_idx_bytes, ws_depth, nfolds; off / sz: R_COUNT regions; fold: nfolds
+// x {m_in, m_out, buf}; consts: the constants the test's invariants are written in.  -> R_COUNT.
+int sim_msm_plan(const int64_t* in, int64_t* out, uint64_t* off, uint64_t* sz, int* fold, int* consts) {
+  MsmPlanIn pi{};
+  pi.n = (size_t)in[0]; pi.c = (int)in[1]; pi.cus = (int)in[2]; pi.span_blocks = (int)in[3];
+  pi.slices = in[4]; pi.seg = in[5]; pi.red = in[6]; pi.skip = in[7]; pi.chunked_sums = in[8]; pi.sort_packed = in[9];
+  const MsmPlan p = msm_plan(pi);
+  const int64_t v[] = {(int64_t)p.W, (int64_t)p.shape.nwide, (int64_t)p.nb, (int64_t)p.S, (int64_t)p.per, p.wide_digits, (int64_t)p.count_parts,
+                        (int64_t)p.count_nbr, (int64_t)p.hist_bytes, (int64_t)p.scan_chunks, p.lanes_target, p.forced_L, (int64_t)p.span_lanes_max, (int64_t)p.max_segs,
+                        (int64_t)p.red.g[0], (int64_t)p.red.g[1], (int64_t)p.red.g[2], p.red.skip, (int64_t)p.max_g[0], (int64_t)p.max_g[1], (int64_t)p.max_g[2],
+                        (int64_t)p.max_g[3], p.packed, (int64_t)p.bucket_lanes, p.tree, p.block_kernel == WSUM_BLOCK8, (int64_t)p.block_kernel,
+                        (int64_t)p.ws_m, (int64_t)p.ws_nblk, p.ws_mid, (int64_t)p.mid_m, (int64_t)p.mid_nblk, (int64_t)p.top_m,
+                        (int64_t)p.top_nblk, (int64_t)p.top_stride, (int64_t)p.cap0, (int64_t)p.cap1, (int64_t)p.wsb_lds, (int64_t)p.nchunks, (int64_t)p.bytes,
+                        (int64_t)p.partials_bytes, (int64_t)p.tmp_idx_bytes, (int64_t)p.ws_depth, (int64_t)p.nfolds};
+  for (size_t i = 0; i < sizeof v / sizeof v[0]; ++i) out[i] = v[i];
+  for (int r = 0; r < R_COUNT; ++r) { off[r] = p.region[r].offset; sz[r] = p.region[r].bytes; }
+  for (int f = 0; f < p.nfolds; ++f) { fold[3 * f] = p.fold[f].m_in; fold[3 * f + 1] = p.fold[f].m_out; fold[3 * f + 2] = p.fold[f].buf; }
+  const int cs[] = {PT_WORDS, FOLD, (int)SPAN_MIN, NODE_STRIDE, MID_STRIDE, WSM_CAP, R_PARTIALS, R_TMP_IDX, R_FOLD0, MSM_MAX_FOLDS};
+  for (size_t i = 0; i < sizeof cs / sizeof cs[0]; ++i) consts[i] = cs[i];
+  return R_COUNT;
+}
 void sim_scalar_mul_base(const uint32_t* k, size_t n, uint32_t* out) {
   HostFTab ft{g_fbase.data()};
   dcb_rounds<0>(n, out, true,
