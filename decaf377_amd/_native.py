@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/decaf377_amd.h.
+"""ctypes binding of the C ABI declared in include/decaf377_amd.h (and decaf377_amd_resident.h, which it includes).
 
 The shared library is built in-tree by `__graft_entry__.build()` (hipcc, gfx950) as
 decaf377_amd/lib/libdecaf377_amd.so.  There is no CPU fallback: if the library is missing
@@ -45,6 +45,11 @@ EXPORTS = [
     "d377_batch_msm_long", "d377_batch_msm_long_encoded",
     "d377_fixed_bases_create_long", "d377_batch_fixed_long_msm", "d377_fixed_long_msm_plan",
     "d377_batch_msm_mixed", "d377_batch_msm_mixed_encoded",
+]
+# every symbol include/decaf377_amd_resident.h declares (checked by tests/test_resident_sums_host.py)
+RESIDENT_EXPORTS = [
+    "d377_batch_fixed_msm_resident", "d377_batch_fixed_long_msm_resident", "d377_batch_fixed_msm_indexed_resident",
+    "d377_batch_msm_mixed_resident", "d377_batch_msm_mixed_encoded_resident", "d377_check_base_index_resident",
 ]
 
 
@@ -211,10 +216,28 @@ def load():
                  "d377_batch_fixed_msm_indexed", "d377_fixed_bases_create_long", "d377_batch_fixed_long_msm",
                  "d377_fixed_long_msm_plan", "d377_batch_msm_mixed", "d377_batch_msm_mixed_encoded"):
         getattr(lib, name).restype = i32
+    # the resident forms: the host form's arguments behind (ctx, dev, stream), a verdict record where indices go in
+    i64 = ctypes.c_int64
+    resident = {
+        "d377_batch_fixed_msm_resident": [vp, i32, vp, i64, vp, sz, vp, vp],
+        "d377_batch_fixed_long_msm_resident": [vp, i32, vp, i64, vp, sz, vp, vp],
+        "d377_batch_fixed_msm_indexed_resident": [vp, i32, vp, i64, vp, vp, sz, sz, vp, vp, vp],
+        "d377_batch_msm_mixed_resident": [vp, i32, vp, i64, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp],
+        "d377_batch_msm_mixed_encoded_resident": [vp, i32, vp, i64, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp],
+        "d377_check_base_index_resident": [vp, i32, vp, i64, vp, sz, vp],
+    }
+    for name, args in resident.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i32
     _lib = lib
     return lib
 
 
+def error(rc, text):
+    """The exception for return code `rc` with the library's (or, for a refusal the binding makes itself, its own) text."""
+    return (StarvedError if rc == ERR_STARVED else NativeError)("decaf377_amd native call failed (%d): %s" % (rc, text))
+
+
 def check(rc):
     if rc != 0:
-        raise (StarvedError if rc == ERR_STARVED else NativeError)("decaf377_amd native call failed (%d): %s" % (rc, load().d377_last_error().decode()))
+        raise error(rc, load().d377_last_error().decode())

@@ -47,8 +47,9 @@ inline int straus_scratch_reserve(DeviceState& d, hipStream_t s, size_t terms, c
     if (ScratchGuard::capturing(s)) return fail(D377_ERR_ARG, "%s", in_capture);
     int rc;
     if ((rc = d.vb_guard.drain())) return rc;               // a launch on another stream may still be using the old area
-    if (d.bm_scratch) HIP_TRY(hipFree(d.bm_scratch));
+    uint32_t* old = d.bm_scratch;
     d.bm_scratch = nullptr; d.bm_cap = 0;
+    if ((rc = retire_scratch(d, old))) return rc;              // (kept where a captured graph may still point into it)
     if (hipMalloc(&d.bm_scratch, need) != hipSuccess) {
       (void)hipGetLastError();
       return fail(D377_ERR_HIP, "%s", no_memory);
@@ -103,6 +104,32 @@ inline int sums_out_reserve(DeviceState& d, size_t n, bool want_xyzt, uint64_t**
 inline int sums_out_copy(DeviceState& d, size_t n, uint8_t* out32, uint64_t* xyzt_out) {
   HIP_TRY(hipMemcpyAsync(out32, d.buf[2], n * 32, hipMemcpyDeviceToHost, d.stream));
   if (xyzt_out) HIP_TRY(hipMemcpyAsync(xyzt_out, d.buf[2] + n * 32, n * 128, hipMemcpyDeviceToHost, d.stream));
+  return D377_OK;
+}
+
+// ---- the resident (device-pointer) forms of the sums over registered bases (fixed_bases.hip, batch_msm_mixed.hip)
+inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// What those forms share once the call's own range and null checks have passed: ctx, dev, the handle,
+// the alignment of the record buffers (16 bytes), of the indices (4) and of the verdict (8), then the device is selected.
+// The caller holds ctx->mu.
+struct ResidentCall {
+  DeviceState* d = nullptr;
+  const FixedBases* fb = nullptr;
+  const uint32_t* tab = nullptr;
+};
+inline int resident_enter(const char* who, d377_ctx* ctx, int dev, int64_t handle, const void* const* rec16, int nrec, const int* index,
+                          const uint64_t* verdict, ResidentCall* rc) {
+  if (dev < 0 || (size_t)dev >= ctx->devs.size()) return fail(D377_ERR_ARG, "%s: dev is not a device of this context", who);
+  rc->fb = fixed_bases_find(ctx, handle);
+  if (!rc->fb) return fail(D377_ERR_ARG, "%s: handle is not a live registration of this context", who);
+  for (int k = 0; k < nrec; ++k)
+    if (!aligned16(rec16[k])) return fail(D377_ERR_ARG, "%s: device record buffers must be 16-byte aligned", who);
+  if (!aligned_to(index, 4)) return fail(D377_ERR_ARG, "%s: base_index must be 4-byte aligned", who);
+  if (!aligned_to(verdict, 8)) return fail(D377_ERR_ARG, "%s: verdict must be 8-byte aligned", who);
+  rc->d = &ctx->devs[(size_t)dev];
+  rc->tab = rc->fb->tab[(size_t)dev];
+  HIP_TRY(hipSetDevice(rc->d->id));
   return D377_OK;
 }
 

@@ -143,8 +143,9 @@ int ensure_partials(DeviceState& d, size_t bytes) {
   if (bytes <= d.bml_cap) return D377_OK;
   int rc;
   if ((rc = d.vb_guard.drain())) return rc;                  // (every user of the area queues behind the guard)
-  if (d.bml_partials) HIP_TRY(hipFree(d.bml_partials));
+  uint8_t* old = d.bml_partials;
   d.bml_partials = nullptr; d.bml_cap = 0;
+  if ((rc = retire_scratch(d, old))) return rc;              // (kept where a captured graph may still point into it)
   const size_t want = bytes + bytes / 4 + 4096;
   if (hipMalloc(&d.bml_partials, want) != hipSuccess) {
     (void)hipGetLastError();

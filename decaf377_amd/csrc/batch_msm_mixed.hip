@@ -15,6 +15,8 @@
 //                     handle's combs with k_fixed_msm_indexed_lane's loader.
 //
 // There is no wave-per-sum route: the lane kernel takes every n, so a small batch is as long as one chain.
+// d377_batch_msm_mixed[_encoded]_resident is the same launcher on device pointers and the caller's stream; it does not read the
+// indices on the host and has fixed_bases.hip's k_index_verdict write one verdict record per call instead.
 //
 // A translation unit of its own, like batch_msm.hip: the register tables of the other units' kernels are measured artefacts.
 #include <hip/hip_runtime.h>
@@ -46,7 +48,8 @@ static_assert(VB_ENTRIES == 9, "straus_sum stores entries 0 .. 8 of every point'
 
 // One lane per sum.  The variable half is k_batch_msm_lane's body, the fixed half k_fixed_msm_indexed_lane's: an absent term
 // (-1) walks scalar 0 on comb 0, and the unsigned compare treats every index outside 0 .. m-1 as absent, so no index can
-// address past the m combs (the host has refused those before the launch all the same).
+// address past the m combs (the host form has refused those before the launch all the same; the resident form counts them
+// in its verdict record, fixed_bases.hip: k_index_verdict).
 template <int BITS, bool ENCODED>
 __global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD)
 k_batch_msm_mixed_lane(SqrtTables T, const uint32_t* tabs, const int* base_index, const uint8_t* fixed_scalar32, int m, int t,
@@ -166,11 +169,9 @@ int mixed_one(DeviceState& d, const FixedBases& fb, const uint32_t* combs, const
   });
 }
 
-// host pointers: every argument checked before any copy or launch, then contiguous slices of the SUMS over the context's
-// devices (host_state.hpp: slice_over_devices)
-int mixed_host(const char* who, d377_ctx* ctx, int64_t handle, const int* base_index, const uint8_t* fixed_scalar32, size_t t,
-               bool encoded, const void* pts_in, const uint8_t* var_scalar32, size_t v, size_t n, uint8_t* enc32_out,
-               uint64_t* xyzt_out, uint8_t* status) {
+// the checks both forms make first, before ctx is looked at: v, t, then null buffers when n > 0
+int mixed_check(const char* who, const int* base_index, const uint8_t* fixed_scalar32, size_t t, bool encoded, const void* pts_in,
+                const uint8_t* var_scalar32, size_t v, size_t n, const uint8_t* enc32_out, const uint8_t* status) {
   if (v < 1 || v > (size_t)MX_VAR_MAX)
     return fail(D377_ERR_ARG, "%s: v must be 1 .. 8 variable terms per sum (D377_BATCH_MSM_MIXED_MAX_VAR); d377_batch_fixed_msm_indexed serves v = 0", who);
   if (t < 1 || t > (size_t)MX_FIXED_MAX)
@@ -183,6 +184,15 @@ int mixed_host(const char* who, d377_ctx* ctx, int64_t handle, const int* base_i
       return D377_ERR_ARG;
     }
   }
+  return D377_OK;
+}
+
+// host pointers: every argument checked before any copy or launch, then contiguous slices of the SUMS over the context's
+// devices (host_state.hpp: slice_over_devices)
+int mixed_host(const char* who, d377_ctx* ctx, int64_t handle, const int* base_index, const uint8_t* fixed_scalar32, size_t t,
+               bool encoded, const void* pts_in, const uint8_t* var_scalar32, size_t v, size_t n, uint8_t* enc32_out,
+               uint64_t* xyzt_out, uint8_t* status) {
+  if (int rc = mixed_check(who, base_index, fixed_scalar32, t, encoded, pts_in, var_scalar32, v, n, enc32_out, status)) return rc;
   if (!ctx) return fail(D377_ERR_ARG, "%s: ctx is null", who);
   std::lock_guard<std::mutex> lock(ctx->mu);
   const FixedBases* fb = fixed_bases_find(ctx, handle);
@@ -210,9 +220,42 @@ int mixed_host(const char* who, d377_ctx* ctx, int64_t handle, const int* base_i
   });
 }
 
+// device pointers: mixed_host's checks in its order up to the handle -- then dev, the handle and alignment instead of the walk
+// over the indices, which the verdict kernel makes on the device in front of the sums kernel (index_verdict.hpp)
+int mixed_resident(const char* who, d377_ctx* ctx, int dev, void* stream, int64_t handle, const int* base_index,
+                   const uint8_t* fixed_scalar32, size_t t, bool encoded, const void* pts_in, const uint8_t* var_scalar32, size_t v,
+                   size_t n, uint8_t* enc32_out, uint64_t* xyzt_out, uint8_t* status, uint64_t* verdict) {
+  if (int rc = mixed_check(who, base_index, fixed_scalar32, t, encoded, pts_in, var_scalar32, v, n, enc32_out, status)) return rc;
+  if (!ctx) return fail(D377_ERR_ARG, "%s: ctx is null", who);
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  ResidentCall c;
+  const void* rec[5] = {fixed_scalar32, pts_in, var_scalar32, enc32_out, xyzt_out};
+  int rc;
+  if ((rc = resident_enter(who, ctx, dev, handle, rec, 5, base_index, verdict, &c))) return rc;
+  if (n > SIZE_MAX / 128 / (t > v ? t : v)) return fail(D377_ERR_ARG, "%s: n x t or n x v overflows", who);
+  if (n == 0) return D377_OK;
+  if (verdict && (rc = index_verdict_launch(*c.d, (hipStream_t)stream, base_index, n * t, (int)c.fb->m, verdict))) return rc;
+  const MixedArgs a{c.tab, (int)c.fb->m, c.fb->bits, base_index, fixed_scalar32, t, encoded, pts_in, var_scalar32, v};
+  return mixed_launch(*c.d, (hipStream_t)stream, a, n, enc32_out, xyzt_out, status);
+}
+
 }  // namespace
 
 extern "C" {
+
+int d377_batch_msm_mixed_resident(d377_ctx* ctx, int dev, void* stream, int64_t handle, const int* base_index,
+                                  const uint8_t* fixed_scalar32, size_t t, const uint64_t* xyzt, const uint8_t* var_scalar32, size_t v,
+                                  size_t n, uint8_t* enc32_out, uint64_t* xyzt_out, uint64_t* verdict) {
+  return mixed_resident("d377_batch_msm_mixed_resident", ctx, dev, stream, handle, base_index, fixed_scalar32, t, false, xyzt,
+                        var_scalar32, v, n, enc32_out, xyzt_out, nullptr, verdict);
+}
+int d377_batch_msm_mixed_encoded_resident(d377_ctx* ctx, int dev, void* stream, int64_t handle, const int* base_index,
+                                          const uint8_t* fixed_scalar32, size_t t, const uint8_t* enc32, const uint8_t* var_scalar32,
+                                          size_t v, size_t n, uint8_t* enc32_out, uint64_t* xyzt_out, uint8_t* status,
+                                          uint64_t* verdict) {
+  return mixed_resident("d377_batch_msm_mixed_encoded_resident", ctx, dev, stream, handle, base_index, fixed_scalar32, t, true,
+                        enc32, var_scalar32, v, n, enc32_out, xyzt_out, status, verdict);
+}
 
 int d377_batch_msm_mixed(d377_ctx* ctx, int64_t handle, const int* base_index, const uint8_t* fixed_scalar32, size_t t,
                          const uint64_t* xyzt, const uint8_t* var_scalar32, size_t v, size_t n, uint8_t* enc32_out,

@@ -1550,6 +1550,8 @@ void free_device(DeviceState& d) {
   (void)hipFree(d.msm.mem);
   for (uint8_t* r : d.msm.retired) (void)hipFree(r);
   d.msm.retired.clear();
+  for (void* r : d.vb_retired) (void)hipFree(r);
+  d.vb_retired.clear();
   if (d.stream) (void)hipStreamDestroy(d.stream);
 }
 

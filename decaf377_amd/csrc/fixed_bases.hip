@@ -8,6 +8,9 @@
 //   d377_batch_fixed_long_msm      the dense sums with every sum cut into g segments of consecutive bases
 //                             (fixed_msm_long_plan.hpp), one lane per segment (k_fixed_msm_seg); the segments' partial sums are
 //                             folded and compressed as d377_batch_msm_long's are (msm_long_fold.hpp).  g = 1: the kernel above
+//   d377_batch_fixed_*_resident    the three kinds of sums on device pointers and a stream: the same launchers without the
+//                             staging frame.  The indexed form does not read its indices on the host: k_index_verdict
+//                             (index_verdict.hpp) writes one record per call, and d377_check_base_index_resident runs it alone
 //
 // The sum is k_scalar_mul_base's walk widened to m combs (curve.hpp: ge_fixed_msm_w8): each base's scalar is reduced and
 // halved, its W signed digits pick one entry per window, and all m x W mixed additions go into ONE accumulator -- no
@@ -37,6 +40,7 @@
 #include "codec_chunked.hpp"
 #include "fixed_msm_long_plan.hpp"
 #include "msm_long_fold.hpp"
+#include "index_verdict.hpp"
 
 using namespace d377;
 
@@ -75,9 +79,9 @@ k_fixed_msm_lane(SqrtTables T, const uint32_t* tabs, const uint8_t* scalar32, in
 
 // The sum whose terms name their bases: term p of lane i walks comb base_index[i t + p].  The lanes of a wave gather from
 // different combs; their control flow is the dense kernel's.  An absent term (-1) walks scalar 0 on comb 0, entry 0 of every
-// window, the identity record.  The host has refused every other index outside 0 .. m-1 before the launch
-// (d377_batch_fixed_msm_indexed); the unsigned compare below treats one as absent all the same, so no index can address past
-// the m combs.
+// window, the identity record.  The host form has refused every other index outside 0 .. m-1 before the launch
+// (d377_batch_fixed_msm_indexed); the resident form has not read them, and its contract is what the unsigned compare below
+// does: such an index is walked as an absent term, so no index can address past the m combs (k_index_verdict counts them).
 template <int BITS>
 __global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD)
 k_fixed_msm_indexed_lane(SqrtTables T, const uint32_t* tabs, const int* base_index, const uint8_t* scalar32, int m, int t, size_t n,
@@ -141,6 +145,30 @@ k_fixed_msm_seg(SqrtTables T, const uint32_t* tabs, const uint8_t* scalar32, Fix
     const ge sum = ge_double_fast(r, true);
     D377_INVARIANT(T, sum, true);
     store_ge_mont256(partials, s * plan.g + q, sum);
+  }
+}
+
+// The verdict on a resident call's indices (index_verdict.hpp): a grid-stride pass over `count` ints.  Every lane joins the
+// verdicts of its entries, the lanes of a wave join theirs by butterfly shuffles, and lane 0 of a wave that found an
+// offender adds its count to verdict[0] and lowers verdict[1] to its first position: at most one atomic of each kind per
+// wave, none for a clean array.  k_index_verdict_init writes the record (0, none) in front of it on the same stream.
+__global__ void k_index_verdict_init(uint64_t* verdict) {
+  if (threadIdx.x == 0) verdict[0] = 0;
+  if (threadIdx.x == 1) verdict[1] = INDEX_VERDICT_NONE;
+}
+__global__ void __launch_bounds__(BLOCK) k_index_verdict(const int* base_index, size_t count, int m, uint64_t* verdict) {
+  static_assert(BLOCK % 64 == 0, "whole waves: every lane takes part in the shuffles");
+  IndexVerdict v = verdict_none();
+  for (size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x; p < count; p += (size_t)gridDim.x * BLOCK)
+    v = verdict_join(v, verdict_of(base_index[p], m, (uint64_t)p));
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const IndexVerdict o{(uint64_t)__shfl_xor((unsigned long long)v.count, off, 64), (uint64_t)__shfl_xor((unsigned long long)v.first, off, 64)};
+    v = verdict_join(v, o);
+  }
+  if ((threadIdx.x & 63) == 0 && v.count != 0) {
+    atomicAdd(reinterpret_cast<unsigned long long*>(verdict), (unsigned long long)v.count);
+    atomicMin(reinterpret_cast<unsigned long long*>(verdict) + 1, (unsigned long long)v.first);
   }
 }
 
@@ -353,7 +381,39 @@ void fixed_bases_release_all(d377_ctx* ctx) {
   ctx->fixed.clear();
 }
 FixedBases* fixed_bases_find(d377_ctx* ctx, int64_t handle) { return find(ctx, handle); }
+
+// No scratch and no lane set: nothing to guard, and nothing that could starve.
+int index_verdict_launch(DeviceState& d, hipStream_t s, const int* base_index, size_t count, int m, uint64_t* verdict) {
+  hipLaunchKernelGGL(k_index_verdict_init, dim3(1), dim3(64), 0, s, verdict);
+  HIP_TRY(hipGetLastError());
+  if (count == 0) return D377_OK;
+  size_t grid = (count + BLOCK - 1) / BLOCK;
+  if (grid > (size_t)d.cus * 8) grid = (size_t)d.cus * 8;    // (as the fold's)
+  hipLaunchKernelGGL(k_index_verdict, dim3((unsigned)grid), dim3(BLOCK), 0, s, base_index, count, m, verdict);
+  HIP_TRY(hipGetLastError());
+  return D377_OK;
+}
 }  // namespace d377
+
+namespace {
+
+// the dense sums on device pointers; cut: every sum in segments (a handle of more than 64 bases is always cut, as on the host)
+int fixed_msm_resident(const char* who, d377_ctx* ctx, int dev, void* stream, int64_t handle, bool cut, const uint8_t* scalar32,
+                       size_t n, uint8_t* enc32_out, uint64_t* xyzt_out) {
+  if (!ctx) return fail(D377_ERR_ARG, "%s: ctx is null", who);
+  if (n && (!scalar32 || !enc32_out)) return fail(D377_ERR_ARG, "%s: null buffer", who);
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  ResidentCall c;
+  const void* rec[3] = {scalar32, enc32_out, xyzt_out};
+  int rc;
+  if ((rc = resident_enter(who, ctx, dev, handle, rec, 3, nullptr, nullptr, &c))) return rc;
+  if (n > SIZE_MAX / 32 / c.fb->m) return fail(D377_ERR_ARG, "%s: n x m overflows", who);
+  if (cut || c.fb->m > (size_t)FX_MAX)
+    return fixed_msm_long_launch(*c.d, (hipStream_t)stream, *c.fb, c.tab, scalar32, n, enc32_out, xyzt_out);
+  return fixed_msm_launch(*c.d, (hipStream_t)stream, *c.fb, c.tab, nullptr, c.fb->m, scalar32, n, enc32_out, xyzt_out);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -470,6 +530,52 @@ int d377_fixed_long_msm_plan(d377_ctx* ctx, int64_t handle, size_t n, int dev, u
   if (segments) *segments = plan.g;
   if (bases_per_segment) *bases_per_segment = plan.b;
   return D377_OK;
+}
+
+// ---- the resident forms: device pointers, enqueued on `stream`, no host synchronisation (include/decaf377_amd.h)
+int d377_batch_fixed_msm_resident(d377_ctx* ctx, int dev, void* stream, int64_t handle, const uint8_t* scalar32, size_t n,
+                                  uint8_t* enc32_out, uint64_t* xyzt_out) {
+  return fixed_msm_resident("d377_batch_fixed_msm_resident", ctx, dev, stream, handle, false, scalar32, n, enc32_out, xyzt_out);
+}
+int d377_batch_fixed_long_msm_resident(d377_ctx* ctx, int dev, void* stream, int64_t handle, const uint8_t* scalar32, size_t n,
+                                       uint8_t* enc32_out, uint64_t* xyzt_out) {
+  return fixed_msm_resident("d377_batch_fixed_long_msm_resident", ctx, dev, stream, handle, true, scalar32, n, enc32_out, xyzt_out);
+}
+
+// The indices are not read on the host: the verdict kernel counts the refused ones in front of the sums kernel, whose
+// unsigned compare walks a refused index as an absent term.
+int d377_batch_fixed_msm_indexed_resident(d377_ctx* ctx, int dev, void* stream, int64_t handle, const int* base_index,
+                                          const uint8_t* scalar32, size_t t, size_t n, uint8_t* enc32_out, uint64_t* xyzt_out,
+                                          uint64_t* verdict) {
+  const char* who = "d377_batch_fixed_msm_indexed_resident";
+  if (t < 1 || t > (size_t)FX_MAX) return fail(D377_ERR_ARG, "%s: t must be 1 .. 64 terms per sum (D377_FIXED_BASES_MAX)", who);
+  if (n && !base_index) return fail(D377_ERR_ARG, "%s: base_index is null", who);
+  if (n && !scalar32) return fail(D377_ERR_ARG, "%s: scalar32 is null", who);
+  if (n && !enc32_out) return fail(D377_ERR_ARG, "%s: enc32_out is null", who);
+  if (!ctx) return fail(D377_ERR_ARG, "%s: ctx is null", who);
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  ResidentCall c;
+  const void* rec[3] = {scalar32, enc32_out, xyzt_out};
+  int rc;
+  if ((rc = resident_enter(who, ctx, dev, handle, rec, 3, base_index, verdict, &c))) return rc;
+  if (n > SIZE_MAX / 32 / t) return fail(D377_ERR_ARG, "%s: n x t overflows", who);
+  if (n == 0) return D377_OK;
+  if (verdict && (rc = index_verdict_launch(*c.d, (hipStream_t)stream, base_index, n * t, (int)c.fb->m, verdict))) return rc;
+  return fixed_msm_launch(*c.d, (hipStream_t)stream, *c.fb, c.tab, base_index, t, scalar32, n, enc32_out, xyzt_out);
+}
+
+// the verdict alone: for callers that want the host form's "nothing is computed" and read the record before they launch
+int d377_check_base_index_resident(d377_ctx* ctx, int dev, void* stream, int64_t handle, const int* base_index, size_t count,
+                                   uint64_t* verdict) {
+  const char* who = "d377_check_base_index_resident";
+  if (count && !base_index) return fail(D377_ERR_ARG, "%s: base_index is null", who);
+  if (!verdict) return fail(D377_ERR_ARG, "%s: verdict is null", who);
+  if (!ctx) return fail(D377_ERR_ARG, "%s: ctx is null", who);
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  ResidentCall c;
+  int rc;
+  if ((rc = resident_enter(who, ctx, dev, handle, nullptr, 0, base_index, verdict, &c))) return rc;
+  return index_verdict_launch(*c.d, (hipStream_t)stream, base_index, count, (int)c.fb->m, verdict);
 }
 
 }  // extern "C"

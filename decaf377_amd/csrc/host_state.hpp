@@ -133,6 +133,7 @@ struct DeviceState {
   int vb_blocks = 0;
   uint32_t* inv_fail = nullptr;          // device counter of the -DD377_CHECK_INVARIANTS build (always allocated)
   ScratchGuard vb_guard;
+  std::vector<void*> vb_retired;         // outgrown table scratch / partials areas a captured graph may still name: freed with the context (retire_scratch)
   hipStream_t stream = nullptr;          // compute stream of the host-pointer entry points
   hipStream_t copy_stream = nullptr;     // PCIe copies of the pipelined host path
   hipStream_t ctl_stream = nullptr;      // highest priority: d377_ctx_health / d377_ctx_reset_scratch (a hardware queue no kernel of ours waits in)
@@ -203,6 +204,16 @@ inline int ensure_shard(DeviceState& d, int slot, size_t bytes) { return grow(d.
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// An outgrown scratch area of the lane-set guard (the Straus table scratch, the long sums' partials): freed -- unless a
+// launch on the guard's areas has been captured into a hipGraph, which then still holds the pointer: from then on the area
+// is retired and kept until d377_ctx_destroy, as the MSM workspace is (MsmWorkspace).  The caller has drained the guard.
+inline int retire_scratch(DeviceState& d, void* area) {
+  if (!area) return D377_OK;
+  if (d.vb_guard.seen_capture) d.vb_retired.push_back(area);
+  else HIP_TRY(hipFree(area));
+  return D377_OK;
+}
+
 // Synchronises a set of streams when the enclosing function returns with an error after work has been
 // enqueued: no copy into caller memory (or into a local vector) may still be in flight once we return.
 struct SyncOnError {
@@ -256,6 +267,9 @@ struct FixedBases;
 void fixed_bases_release_all(d377_ctx* ctx);
 // fixed_bases.hip: the live registration `handle` of the context, or null (batch_msm_mixed.hip).  Caller holds ctx->mu.
 FixedBases* fixed_bases_find(d377_ctx* ctx, int64_t handle);
+// fixed_bases.hip: the verdict on `count` base indices against m bases (index_verdict.hpp), enqueued on `s`: the record's
+// initialisation and k_index_verdict.  count == 0 leaves the record (0, none).  Caller holds ctx->mu.
+int index_verdict_launch(DeviceState& d, hipStream_t s, const int* base_index, size_t count, int m, uint64_t* verdict);
 
 }  // namespace d377
 

@@ -30,6 +30,18 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+def _torch_stream(dev):
+    """torch's current stream on `dev`, as the hipStream_t argument of a device-pointer call."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _cuda_device(ctx, *arrays):
+    """The device of the first tensor among `arrays` that lives on a device of `ctx`, or None: which calls take the resident
+    forms.  Every other input -- numpy, CPU tensors, tensors on a GPU the context does not own -- keeps the host path."""
+    return next((a.device for a in arrays if _is_torch(a) and a.device.type == "cuda" and a.device.index in ctx.device_ids), None)
+
+
 def _rows(a):
     if a.ndim < 1:
         raise ValueError("expected a [n, k] array of packed records")
@@ -679,8 +691,11 @@ class FixedBases:
 
     def msm(self, scalar32, elements=False):
         """n sums over the registered bases: scalar32 [n * m, 32] u8, term-major within a sum (any 32 bytes, reduced mod r)
-        -> enc [n, 32] u8, or (enc, xyzt [n, 16]) with elements=True.  A torch tensor is STAGED through host memory (the
-        library has no device-pointer form of this call) and the results come back on its device."""
+        -> enc [n, 32] u8, or (enc, xyzt [n, 16]) with elements=True.  A numpy array or a CPU tensor takes the host-pointer
+        call, and so does a tensor on a GPU the context does not own (staged through host memory, the results back on its
+        device); a tensor on a device of the context takes d377_batch_fixed_msm_resident on torch's current stream, with
+        no copy and no synchronisation, and the results are allocated on its device -- on that ONE device: a multi-GPU
+        context slices host arrays over its devices, never a resident tensor."""
         return self._dense("d377_batch_fixed_msm", "FixedBases.msm", scalar32, elements)
 
     def msm_long(self, scalar32, elements=False):
@@ -696,8 +711,47 @@ class FixedBases:
         _native.check(self._lib.d377_fixed_long_msm_plan(self.ctx._h, self._live(), ctypes.c_size_t(n), int(dev), ctypes.byref(g), ctypes.byref(b)))
         return int(g.value), int(b.value)
 
+    def _on_device(self, dev, a):
+        """`a` as a contiguous tensor on `dev` (a numpy array or a tensor that lives elsewhere is copied there)."""
+        import torch
+        if not _is_torch(a):
+            a = np.ascontiguousarray(a)
+            a = torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a)
+        return a.detach().to(dev).contiguous()
+
+    def _outputs(self, what, dev, n, elements, status_rows=None, outs=None):
+        """The outputs of a resident call on `dev`: enc [n, 32], xyzt [n, 16] with elements, status [status_rows] for
+        Encodings -- allocated there, or the caller's `outs` in that order, checked like inputs."""
+        import torch
+        specs = [(ENC, n)] + ([(ELEM, n)] if elements else []) + ([(FLAG, status_rows)] if status_rows is not None else [])
+        if outs is None:
+            return [torch.empty((rows,) + tail, dtype=torch.uint8 if k == "u8" else torch.int64, device=dev) for (tail, k), rows in specs]
+        if len(outs) != len(specs):
+            raise ValueError("%s: %d output arrays expected" % (what, len(specs)))
+        for a, (spec, rows) in zip(outs, specs):
+            if not _is_torch(a):
+                raise ValueError(what + ": outs must be tensors on the inputs' device")
+            _check(a, spec, rows, what + " output", dev)
+            if not a.is_contiguous():
+                raise ValueError(what + " output must be contiguous")
+        return list(outs)
+
     def _dense(self, symbol, what, scalar32, elements):
         h = self._live()
+        dev = _cuda_device(self.ctx, scalar32)
+        if dev is not None:                                   # resident: no copy, no synchronisation, torch's current stream
+            di = self.ctx._dev_index(dev)
+            sc = scalar32.detach().contiguous()
+            terms = _rows(sc)
+            if terms % self.m:
+                raise ValueError("%s: the number of scalars must be a multiple of m = %d" % (what, self.m))
+            n = terms // self.m
+            _check(sc, ENC, terms, what + " scalars")
+            outs = self._outputs(what, dev, n, elements)
+            p = lambda t: ctypes.c_void_p(t.data_ptr())
+            _native.check(getattr(self._lib, symbol + "_resident")(self.ctx._h, di, _torch_stream(dev), h, p(sc), ctypes.c_size_t(n),
+                                                                   p(outs[0]), p(outs[1]) if elements else None))
+            return tuple(outs) if elements else outs[0]
         tdev = scalar32.device if _is_torch(scalar32) else None
         sc = np.ascontiguousarray(scalar32.detach().cpu().numpy() if tdev is not None else scalar32)
         terms = _rows(sc)
@@ -716,17 +770,94 @@ class FixedBases:
                 xyzt = torch.from_numpy(xyzt.view(np.int64)).to(tdev)
         return (enc, xyzt) if elements else enc
 
-    def msm_indexed(self, base_index, scalar32, elements=False):
+    def _resident_index(self, dev, base_index, what):
+        """base_index as a contiguous [n, t] int32 tensor on `dev`; an int64 index outside 32 bits is the ValueError of the
+        host path (one synchronising reduction, for int64 tensors only)."""
+        import torch
+        idx = base_index if _is_torch(base_index) else torch.from_numpy(np.ascontiguousarray(base_index))
+        if idx.ndim != 2 or idx.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+            raise ValueError(what + ": base_index must be an [n, t] integer array")
+        idx = idx.detach().to(dev)
+        if idx.dtype != torch.int32:
+            if idx.numel() and (int(idx.min()) < -(1 << 31) or int(idx.max()) >= (1 << 31)):
+                raise ValueError(what + ": base_index does not fit 32 bits")
+            idx = idx.to(torch.int32)
+        return idx.contiguous()
+
+    @staticmethod
+    def _verdict_tensor(dev, n):
+        """The [2] int64 record a resident call writes; a call of no sums enqueues nothing, so its record is made here."""
+        import torch
+        verdict = torch.zeros((2,), dtype=torch.int64, device=dev)
+        if n == 0:
+            verdict[1] = -1
+        return verdict
+
+    def _verdict(self, dev, di, idx, symbol):
+        """check_indices=True: d377_check_base_index_resident, then the one synchronisation -- the 16-byte record is read, and on
+        a refused index NativeError with the host form's text is raised before any sum is launched."""
+        import torch
+        verdict = torch.empty((2,), dtype=torch.int64, device=dev)
+        _native.check(self._lib.d377_check_base_index_resident(self.ctx._h, di, _torch_stream(dev), self._live(), ctypes.c_void_p(idx.data_ptr()),
+                                                               ctypes.c_size_t(idx.numel()), ctypes.c_void_p(verdict.data_ptr())))
+        count, first = (int(x) & ((1 << 64) - 1) for x in verdict.cpu().tolist())
+        if count:
+            t = int(idx.shape[1])
+            b = int(idx.reshape(-1)[first].item())
+            # the host form's text (fixed_bases.hip, batch_msm_mixed.hip), restated: the library has made no refusal whose text
+            # could be read.  tests/test_resident_sums_gpu.py::test_python_checks_the_indices_before_any_launch compares the two
+            # and is the only guard against their drifting apart.
+            raise _native.error(-2, "%s: base_index[%d] = %d (sum %d, term %d) is neither -1 nor a base 0 .. %d of this registration"
+                                % (symbol, first, b, first // t, first % t, self.m - 1))
+
+    def msm_indexed(self, base_index, scalar32, elements=False, check_indices=True, outs=None):
         """n sums of t terms that name their bases (d377_batch_fixed_msm_indexed):
 
             out[i] = sum over j < t of scalars[i t + j] * B_{base_index[i, j]}
 
         base_index: [n, t] int32 (int64 is accepted and range-checked), each 0 .. m-1 or -1 for an absent term -- which
         costs as much as a present one, so t should be the longest sum's length.  scalar32: [n * t, 32] or [n, t, 32] u8,
-        term-major (any 32 bytes, reduced mod r).  -> enc [n, 32] u8, or (enc, xyzt [n, 16]) with elements=True.  A torch
-        tensor is STAGED through host memory, as in msm, and the results come back on the scalars' device (the indices'
-        if the scalars are no tensor).  An index outside -1 .. m-1 raises NativeError and nothing is computed."""
+        term-major (any 32 bytes, reduced mod r).  -> enc [n, 32] u8, or (enc, xyzt [n, 16]) with elements=True.  An index
+        outside -1 .. m-1 raises NativeError and nothing is computed.
+        numpy arrays, CPU tensors and tensors on a GPU the context does not own take the host-pointer call (staged, sliced
+        over the devices of a multi-GPU context).  When the scalars or the indices are a tensor on a device of the context
+        the call runs on that one device: it is d377_batch_fixed_msm_indexed_resident on torch's current stream (the other argument is
+        copied to that device if it lives elsewhere) and the results are allocated there.  check_indices=True first runs the
+        index verdict alone and reads its 16-byte record -- the call's one synchronisation -- so that a refused index raises
+        as above, with no sum launched.  check_indices=False is fully asynchronous: nothing is read, the verdict tensor
+        ([2] int64: the count of refused indices, the first position or -1 = UINT64_MAX) is appended to the returned tuple,
+        and a refused index has contributed nothing to its sum.  outs, a supported part of this route as of msm_small's
+        and msm_long's: preallocated contiguous tensors on that device in the order of the result, without the verdict, for
+        callers that keep their buffers (a captured graph, a pipeline); the host route allocates its own arrays and
+        refuses outs with ValueError."""
         h = self._live()
+        dev = _cuda_device(self.ctx, scalar32, base_index)
+        if dev is not None:
+            what = "FixedBases.msm_indexed"
+            di = self.ctx._dev_index(dev)
+            idx = self._resident_index(dev, base_index, what)
+            n, t = (int(x) for x in idx.shape)
+            sc = self._on_device(dev, scalar32)
+            if sc.ndim == 3:
+                if tuple(sc.shape[:2]) != (n, t):
+                    raise ValueError(what + ": scalars [n, t, 32] must match base_index [n, t]")
+                sc = sc.reshape(n * t, 32)
+            _check(sc, ENC, n * t, what + " scalars")
+            verdict = None
+            if check_indices:
+                self._verdict(dev, di, idx, "d377_batch_fixed_msm_indexed")
+            else:
+                verdict = self._verdict_tensor(dev, n)
+            outs = self._outputs(what, dev, n, elements, outs=outs)
+            p = lambda a: ctypes.c_void_p(a.data_ptr())
+            _native.check(self._lib.d377_batch_fixed_msm_indexed_resident(
+                self.ctx._h, di, _torch_stream(dev), h, p(idx), p(sc), ctypes.c_size_t(t), ctypes.c_size_t(n), p(outs[0]),
+                p(outs[1]) if elements else None, p(verdict) if verdict is not None else None))
+            if verdict is not None:
+                outs.append(verdict)
+            return tuple(outs) if len(outs) > 1 else outs[0]
+        if outs is not None:
+            raise ValueError("FixedBases.msm_indexed: outs goes with tensors on a device of the context")
         tdev = scalar32.device if _is_torch(scalar32) else (base_index.device if _is_torch(base_index) else None)
         idx = np.asarray(base_index.detach().cpu().numpy() if _is_torch(base_index) else base_index)
         if idx.ndim != 2 or idx.dtype.kind not in "iu":
@@ -755,7 +886,7 @@ class FixedBases:
                 xyzt = torch.from_numpy(xyzt.view(np.int64)).to(tdev)
         return (enc, xyzt) if elements else enc
 
-    def msm_mixed(self, base_index, fixed_scalar32, points, var_scalar32, elements=False):
+    def msm_mixed(self, base_index, fixed_scalar32, points, var_scalar32, elements=False, check_indices=True, outs=None):
         """n mixed sums, registered bases plus variable points (d377_batch_msm_mixed[_encoded]):
 
             out[i] = sum over j < t of fixed[i t + j] * B_{base_index[i, j]}  +  sum over p < v of var[i v + p] * P[i v + p]
@@ -764,11 +895,21 @@ class FixedBases:
         fixed_scalar32: [n * t, 32] or [n, t, 32] u8.  points: [n, v, 16] / [n * v, 16] u64 Element records, or [n, v, 32] /
         [n * v, 32] u8 Encodings, 1 <= v <= 8.  var_scalar32: [n * v, 32] or [n, v, 32] u8.  Scalars are any 32 bytes, reduced
         mod r.  -> enc [n, 32] u8, or (enc, xyzt [n, 16]) with elements=True; for Encodings status [n * v] u8 is appended
-        (1 = invalid Encoding, that term left out of its sum): msm_small's order.  A torch tensor is STAGED through host memory,
-        as in msm_indexed, and the results come back on the device of the first tensor among points, the scalars and the
-        indices.  An index outside -1 .. m-1 raises NativeError and nothing is computed."""
+        (1 = invalid Encoding, that term left out of its sum): msm_small's order.  An index outside -1 .. m-1 raises
+        NativeError and nothing is computed.
+        numpy arrays, CPU tensors and tensors on a GPU the context does not own take the host-pointer call.  When any
+        argument is a tensor on a device of the context the call runs on that one device: it is d377_batch_msm_mixed[_encoded]_resident on torch's current stream, on the device of the first such tensor
+        among points, the scalars and the indices (arguments that live elsewhere are copied there), and the results are
+        allocated on it.  check_indices is msm_indexed's: True reads the index verdict first, the one synchronisation, and
+        raises before any sum is launched; False is fully asynchronous and appends the verdict tensor to the result; outs
+        (this route only) are preallocated tensors on that device in the order of the result, without the verdict."""
         what = "FixedBases.msm_mixed"
         h = self._live()
+        dev = _cuda_device(self.ctx, points, var_scalar32, fixed_scalar32, base_index)
+        if dev is not None:
+            return self._mixed_resident(dev, h, base_index, fixed_scalar32, points, var_scalar32, elements, check_indices, outs)
+        if outs is not None:
+            raise ValueError(what + ": outs goes with tensors on a device of the context")
         tdev = next((a.device for a in (points, var_scalar32, fixed_scalar32, base_index) if _is_torch(a)), None)
         host = lambda a: np.asarray(a.detach().cpu().numpy() if _is_torch(a) else a)
         idx = host(base_index)
@@ -826,6 +967,54 @@ class FixedBases:
         if encoded:
             out = out + (status,)
         return out if len(out) > 1 else out[0]
+
+    def _mixed_resident(self, dev, h, base_index, fixed_scalar32, points, var_scalar32, elements, check_indices, outs):
+        """msm_mixed on device buffers: the host path's shape rules on tensors, then the resident call."""
+        import torch
+        what = "FixedBases.msm_mixed"
+        di = self.ctx._dev_index(dev)
+        idx = self._resident_index(dev, base_index, what)
+        n, t = (int(x) for x in idx.shape)
+        fs = self._on_device(dev, fixed_scalar32)
+        if fs.ndim == 3:
+            if tuple(fs.shape[:2]) != (n, t):
+                raise ValueError(what + ": fixed scalars [n, t, 32] must match base_index [n, t]")
+            fs = fs.reshape(n * t, 32)
+        _check(fs, ENC, n * t, what + " fixed scalars")
+        pts = self._on_device(dev, points)
+        if pts.ndim == 3:
+            if int(pts.shape[0]) != n:
+                raise ValueError(what + ": points [n, v, .] must have one row per sum")
+            pts = pts.reshape(pts.shape[0] * pts.shape[1], pts.shape[2])
+        encoded = pts.dtype == torch.uint8
+        terms = _rows(pts)
+        if n == 0 or terms % n:
+            if terms or n:
+                raise ValueError(what + ": the number of points must be a multiple of the number of sums")
+        v = terms // n if n else 1
+        _check(pts, ENC if encoded else ELEM, n * v, what + " points")
+        vs = self._on_device(dev, var_scalar32)
+        if vs.ndim == 3:
+            if tuple(vs.shape[:2]) != (n, v):
+                raise ValueError(what + ": variable scalars [n, v, 32] must match the points [n, v, .]")
+            vs = vs.reshape(n * v, 32)
+        _check(vs, ENC, n * v, what + " variable scalars")
+        symbol = "d377_batch_msm_mixed_encoded" if encoded else "d377_batch_msm_mixed"
+        verdict = None
+        if check_indices:
+            self._verdict(dev, di, idx, symbol)
+        else:
+            verdict = self._verdict_tensor(dev, n)
+        outs = self._outputs(what, dev, n, elements, n * v if encoded else None, outs)
+        p = lambda a: ctypes.c_void_p(a.data_ptr()) if a is not None else None
+        args = [self.ctx._h, di, _torch_stream(dev), h, p(idx), p(fs), ctypes.c_size_t(t), p(pts), p(vs), ctypes.c_size_t(v),
+                ctypes.c_size_t(n), p(outs[0]), p(outs[1]) if elements else None]
+        if encoded:
+            args.append(p(outs[-1]))
+        _native.check(getattr(self._lib, symbol + "_resident")(*args, p(verdict)))
+        if verdict is not None:
+            outs.append(verdict)
+        return tuple(outs) if len(outs) > 1 else outs[0]
 
     def vartime_multiscalar_mul(self, scalars):
         """The sums' Encodings for an Fr batch (or [n * m, 32] array) of n x m scalars, term-major within a sum."""

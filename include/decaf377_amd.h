@@ -350,7 +350,7 @@ int d377_batch_msm_long_encoded(d377_ctx* ctx, const uint8_t* enc32, const uint8
  * sums as Element records (n x 16 u64, some extended representative: equal under d377_batch_eq, same encoding).  Any
  * representative of a base gives the same encodings, one that differs by a torsion point the encoding quotients away
  * included.  m = 1 is a fixed-base multiplication by B_0.  A multi-GPU context slices the SUMS over its devices.
- * Host pointers only: a device-pointer form is not offered (a Python torch tensor is staged through host memory).
+ * The host-pointer form; device buffers take d377_batch_fixed_msm_resident (decaf377_amd_resident.h).
  *
  * d377_batch_fixed_msm_indexed computes n sums of t terms each, 1 <= t <= D377_FIXED_BASES_MAX, whose terms name their
  * bases: enc32_out[i] = the canonical Encoding of
@@ -364,7 +364,8 @@ int d377_batch_msm_long_encoded(d377_ctx* ctx, const uint8_t* enc32, const uint8
  * copy or launch, the message names base_index and the first offending position, and no output is written.  Arguments
  * are checked in this order: t, null base_index / scalar32 / enc32_out (n > 0), ctx, the handle, the indices; n == 0 with
  * good arguments is D377_OK.  With 64 registered bases a two-term sum is 2 W mixed additions where the dense call walks
- * 64 W and uploads 64 scalars.  Host pointers only, sliced over the devices of a multi-GPU context by SUMS, as above.
+ * 64 W and uploads 64 scalars.  The host-pointer form, sliced over the devices of a multi-GPU context by SUMS, as above; device
+ * buffers take d377_batch_fixed_msm_indexed_resident (decaf377_amd_resident.h), which answers the indices with a verdict record.
  *
  * Handles: a handle is a positive integer that names one registration within its context (never reused by that
  * context); every call takes the context and the handle, and a handle that was destroyed, or never created there, is
@@ -398,7 +399,7 @@ int d377_batch_msm_long_encoded(d377_ctx* ctx, const uint8_t* enc32, const uint8
  * bases at 12 bits 2.23 ms against 10.61 ms, 2^8 sums of 4096 bases 2.32 ms against 10.67 ms (12 bits, 22.5 GB of combs) and
  * 2.99 against 10.81 (8 bits), 2^16 sums of 65 bases 8.08 against 43.10; the kernel walks 1.70e10 additions per second over
  * 22.5 GB of combs as over 2.2 GB.  256 sums over a 64-base handle: 0.39 ms against 3.64 ms through d377_batch_fixed_msm.
- * For ONE sum use d377_msm: 0.45 ms against 0.60 ms at 4096 terms.  Host pointers only. */
+ * For ONE sum use d377_msm: 0.45 ms against 0.60 ms at 4096 terms.  Device buffers: d377_batch_fixed_long_msm_resident. */
 #define D377_FIXED_BASES_MAX 64
 #define D377_FIXED_BASES_LONG_MAX 4096
 int d377_fixed_bases_create(d377_ctx* ctx, const uint64_t* xyzt, size_t m, int comb_bits, int64_t* handle_out);
@@ -447,8 +448,8 @@ int d377_fixed_long_msm_plan(d377_ctx* ctx, int64_t handle, size_t n, int dev, u
  * argument and the call that serves 0 of them), null buffers when n > 0 (the message names the buffer), ctx, the handle, then
  * the whole n x t index array (the message names base_index and the first offending position); on a refused call no output
  * byte is written; n == 0 with good arguments is D377_OK.  Scratch: the small sums' table scratch for v terms, grown on
- * demand and kept.  A multi-GPU context slices the SUMS over its devices.  Host pointers only: a device-pointer form is not
- * offered (a Python torch tensor is staged through host memory). */
+ * demand and kept.  A multi-GPU context slices the SUMS over its devices.  These are the host-pointer forms; device buffers take
+ * d377_batch_msm_mixed[_encoded]_resident (decaf377_amd_resident.h), which answer the indices with a verdict record. */
 #define D377_BATCH_MSM_MIXED_MAX_VAR 8      /* = D377_BATCH_MSM_MAX_TERMS */
 int d377_batch_msm_mixed(d377_ctx* ctx, int64_t handle, const int* base_index, const uint8_t* fixed_scalar32, size_t t,
                          const uint64_t* xyzt, const uint8_t* var_scalar32, size_t v, size_t n, uint8_t* enc32_out,
@@ -456,6 +457,11 @@ int d377_batch_msm_mixed(d377_ctx* ctx, int64_t handle, const int* base_index, c
 int d377_batch_msm_mixed_encoded(d377_ctx* ctx, int64_t handle, const int* base_index, const uint8_t* fixed_scalar32, size_t t,
                                  const uint8_t* enc32, const uint8_t* var_scalar32, size_t v, size_t n, uint8_t* enc32_out,
                                  uint64_t* xyzt_out, uint8_t* status);
+
+/* The fixed-base, indexed and mixed sums above also have forms on DEVICE buffers, the resident forms
+ * (d377_batch_fixed_msm_resident, d377_batch_fixed_long_msm_resident, d377_batch_fixed_msm_indexed_resident,
+ * d377_batch_msm_mixed[_encoded]_resident, d377_check_base_index_resident): they are declared in decaf377_amd_resident.h,
+ * which this header includes at its end. */
 
 /* Fq field operations on in-memory elements (4 Montgomery u64 limbs, R = 2^256, fully reduced), the
  * unit everything above is built from             src/fields/fq/u64/wrapper.rs:99-132, fq/ops.rs
@@ -593,4 +599,7 @@ int d377_batch_sharded_dev(d377_ctx* ctx, int root_dev, void* stream, int op, co
 #ifdef __cplusplus
 }
 #endif
+
+#include "decaf377_amd_resident.h"
+
 #endif /* DECAF377_AMD_H */

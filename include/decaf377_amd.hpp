@@ -218,6 +218,49 @@ class FixedBases {
     if (status) status->swap(st);
     return enc;
   }
+  /// The resident forms (d377_batch_*_resident): every pointer is a DEVICE pointer on device `dev` of the Engine (records
+  /// 16-byte aligned), the call enqueues on `stream` (a hipStream_t) and returns without synchronising; n sums.  `elements_out`
+  /// and `verdict` may be null.  The indexed and mixed forms do not refuse a bad index: it contributes nothing and the
+  /// verdict record (two u64 on the device: the count of refused indices, the first position or UINT64_MAX) counts it.
+  void msm_resident(int dev, void* stream, const Fr* scalars, size_t n, Encoding* enc_out, Element* elements_out = nullptr) {
+    live();
+    check(d377_batch_fixed_msm_resident(ctx(), dev, stream, h_, reinterpret_cast<const uint8_t*>(scalars), n,
+                                        reinterpret_cast<uint8_t*>(enc_out), reinterpret_cast<uint64_t*>(elements_out)));
+  }
+  void msm_long_resident(int dev, void* stream, const Fr* scalars, size_t n, Encoding* enc_out, Element* elements_out = nullptr) {
+    live();
+    check(d377_batch_fixed_long_msm_resident(ctx(), dev, stream, h_, reinterpret_cast<const uint8_t*>(scalars), n,
+                                             reinterpret_cast<uint8_t*>(enc_out), reinterpret_cast<uint64_t*>(elements_out)));
+  }
+  void msm_indexed_resident(int dev, void* stream, const int* base_index, const Fr* scalars, size_t t, size_t n, Encoding* enc_out,
+                            Element* elements_out = nullptr, uint64_t* verdict = nullptr) {
+    live();
+    check(d377_batch_fixed_msm_indexed_resident(ctx(), dev, stream, h_, base_index, reinterpret_cast<const uint8_t*>(scalars), t, n,
+                                                reinterpret_cast<uint8_t*>(enc_out), reinterpret_cast<uint64_t*>(elements_out), verdict));
+  }
+  void msm_mixed_resident(int dev, void* stream, const int* base_index, const Fr* fixed_scalars, size_t t, const Element* points,
+                          const Fr* var_scalars, size_t v, size_t n, Encoding* enc_out, Element* elements_out = nullptr,
+                          uint64_t* verdict = nullptr) {
+    live();
+    check(d377_batch_msm_mixed_resident(ctx(), dev, stream, h_, base_index, reinterpret_cast<const uint8_t*>(fixed_scalars), t,
+                                        reinterpret_cast<const uint64_t*>(points), reinterpret_cast<const uint8_t*>(var_scalars), v, n,
+                                        reinterpret_cast<uint8_t*>(enc_out), reinterpret_cast<uint64_t*>(elements_out), verdict));
+  }
+  /// ... over Encodings: status (n x v device bytes) marks the invalid ones
+  void msm_mixed_resident(int dev, void* stream, const int* base_index, const Fr* fixed_scalars, size_t t, const Encoding* points,
+                          const Fr* var_scalars, size_t v, size_t n, Encoding* enc_out, uint8_t* status, Element* elements_out = nullptr,
+                          uint64_t* verdict = nullptr) {
+    live();
+    check(d377_batch_msm_mixed_encoded_resident(ctx(), dev, stream, h_, base_index, reinterpret_cast<const uint8_t*>(fixed_scalars), t,
+                                                reinterpret_cast<const uint8_t*>(points), reinterpret_cast<const uint8_t*>(var_scalars),
+                                                v, n, reinterpret_cast<uint8_t*>(enc_out), reinterpret_cast<uint64_t*>(elements_out),
+                                                status, verdict));
+  }
+  /// The index verdict alone over `count` device ints (d377_check_base_index_resident).
+  void check_base_index_resident(int dev, void* stream, const int* base_index, size_t count, uint64_t* verdict) {
+    live();
+    check(d377_check_base_index_resident(ctx(), dev, stream, h_, base_index, count, verdict));
+  }
   /// table bytes per device
   uint64_t table_bytes() const {
     uint64_t b = 0;
@@ -229,6 +272,8 @@ class FixedBases {
  private:
   friend class Engine;
   FixedBases(Engine* e, int64_t h, size_t m) : eng_(e), h_(h), m_(m) {}
+  void live() const { if (!h_) throw std::logic_error("decaf377_amd: FixedBases used after it was destroyed or its Engine was"); }
+  static void check(int rc) { if (rc != D377_OK) throw DeviceError(rc); }
   void reset();
   d377_ctx* ctx() const;
   Engine* eng_ = nullptr;

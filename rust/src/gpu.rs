@@ -34,6 +34,8 @@ use crate::{Element, Encoding, EncodingError, Fq, Fr};
 
 #[path = "gpu/ffi.rs"]
 pub mod ffi;
+#[path = "gpu/ffi_resident.rs"]
+pub mod ffi_resident;                                             // rust/src/ffi_resident.rs, from include/decaf377_amd_resident.h
 
 /// Which backend's root `sqrt_ratio_zeta_batch` returns (the flags are the same).
 #[derive(Copy, Clone, Debug, PartialEq, Eq)]
@@ -710,5 +712,37 @@ pub mod dev {
     pub unsafe fn sharded(ctx: &GpuContext, root_dev: i32, stream: *mut c_void, op: i32, in0: *const c_void, in1: *const c_void, n: usize,
                           out0: *mut c_void, out1: *mut c_void) -> Result<(), GpuError> {
         check(ffi::d377_batch_sharded_dev(ctx.0, root_dev, stream, op, in0, in1, n, out0, out1))
+    }
+
+    // The resident forms of the sums over registered bases (ffi_resident.rs, d377_batch_*_resident): `xyzt_out` may be null.  The indexed and mixed sums do not
+    // refuse a bad index: it contributes nothing and is counted in `verdict` (two u64 on the device: the count of refused
+    // indices, the first position or u64::MAX), which may be null; `check_base_index_resident` runs the verdict alone.
+    pub unsafe fn fixed_msm_resident(fb: &FixedBases, dev: i32, stream: *mut c_void, scalar32: *const u8, n: usize, enc32_out: *mut u8,
+                                     xyzt_out: *mut u64) -> Result<(), GpuError> {
+        check(ffi_resident::d377_batch_fixed_msm_resident(fb.ctx.0, dev, stream, fb.handle, scalar32, n, enc32_out, xyzt_out))
+    }
+    pub unsafe fn fixed_long_msm_resident(fb: &FixedBases, dev: i32, stream: *mut c_void, scalar32: *const u8, n: usize, enc32_out: *mut u8,
+                                          xyzt_out: *mut u64) -> Result<(), GpuError> {
+        check(ffi_resident::d377_batch_fixed_long_msm_resident(fb.ctx.0, dev, stream, fb.handle, scalar32, n, enc32_out, xyzt_out))
+    }
+    pub unsafe fn fixed_msm_indexed_resident(fb: &FixedBases, dev: i32, stream: *mut c_void, base_index: *const i32, scalar32: *const u8,
+                                             t: usize, n: usize, enc32_out: *mut u8, xyzt_out: *mut u64, verdict: *mut u64) -> Result<(), GpuError> {
+        check(ffi_resident::d377_batch_fixed_msm_indexed_resident(fb.ctx.0, dev, stream, fb.handle, base_index, scalar32, t, n, enc32_out, xyzt_out, verdict))
+    }
+    pub unsafe fn msm_mixed_resident(fb: &FixedBases, dev: i32, stream: *mut c_void, base_index: *const i32, fixed_scalar32: *const u8, t: usize,
+                                     xyzt: *const u64, var_scalar32: *const u8, v: usize, n: usize, enc32_out: *mut u8, xyzt_out: *mut u64,
+                                     verdict: *mut u64) -> Result<(), GpuError> {
+        check(ffi_resident::d377_batch_msm_mixed_resident(fb.ctx.0, dev, stream, fb.handle, base_index, fixed_scalar32, t, xyzt, var_scalar32, v, n,
+                                                 enc32_out, xyzt_out, verdict))
+    }
+    pub unsafe fn msm_mixed_encoded_resident(fb: &FixedBases, dev: i32, stream: *mut c_void, base_index: *const i32, fixed_scalar32: *const u8,
+                                             t: usize, enc32: *const u8, var_scalar32: *const u8, v: usize, n: usize, enc32_out: *mut u8,
+                                             xyzt_out: *mut u64, status: *mut u8, verdict: *mut u64) -> Result<(), GpuError> {
+        check(ffi_resident::d377_batch_msm_mixed_encoded_resident(fb.ctx.0, dev, stream, fb.handle, base_index, fixed_scalar32, t, enc32, var_scalar32,
+                                                         v, n, enc32_out, xyzt_out, status, verdict))
+    }
+    pub unsafe fn check_base_index_resident(fb: &FixedBases, dev: i32, stream: *mut c_void, base_index: *const i32, count: usize,
+                                            verdict: *mut u64) -> Result<(), GpuError> {
+        check(ffi_resident::d377_check_base_index_resident(fb.ctx.0, dev, stream, fb.handle, base_index, count, verdict))
     }
 }
