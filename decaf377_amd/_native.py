@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/decaf377_amd.h (and decaf377_amd_resident.h, which it includes).
+"""ctypes binding of the C ABI declared in include/decaf377_amd.h (and decaf377_amd_resident.h and decaf377_amd_long_sums.h, which it includes).
 
 The shared library is built in-tree by `__graft_entry__.build()` (hipcc, gfx950) as
 decaf377_amd/lib/libdecaf377_amd.so.  There is no CPU fallback: if the library is missing
@@ -50,6 +50,11 @@ EXPORTS = [
 RESIDENT_EXPORTS = [
     "d377_batch_fixed_msm_resident", "d377_batch_fixed_long_msm_resident", "d377_batch_fixed_msm_indexed_resident",
     "d377_batch_msm_mixed_resident", "d377_batch_msm_mixed_encoded_resident", "d377_check_base_index_resident",
+]
+# every symbol include/decaf377_amd_long_sums.h declares (checked by tests/test_msm_long_indexed_host.py)
+LONG_SUMS_EXPORTS = [
+    "d377_batch_long_msm_resident", "d377_batch_long_msm_encoded_resident", "d377_batch_long_msm_indexed",
+    "d377_batch_long_msm_indexed_resident",
 ]
 
 
@@ -226,6 +231,13 @@ def load():
         "d377_batch_msm_mixed_encoded_resident": [vp, i32, vp, i64, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp],
         "d377_check_base_index_resident": [vp, i32, vp, i64, vp, sz, vp],
     }
+    # the long sums on device buffers and over a pool (decaf377_amd_long_sums.h)
+    resident.update({
+        "d377_batch_long_msm_resident": [vp, i32, vp, vp, vp, sz, sz, vp, vp],
+        "d377_batch_long_msm_encoded_resident": [vp, i32, vp, vp, vp, sz, sz, vp, vp, vp],
+        "d377_batch_long_msm_indexed": [vp, vp, sz, vp, vp, sz, sz, vp, vp],
+        "d377_batch_long_msm_indexed_resident": [vp, i32, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp],
+    })
     for name, args in resident.items():
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = i32

@@ -1,5 +1,5 @@
-// batch_host.hpp -- the host launch path the batched-sum units share (batch_msm.hip, batch_msm_long.hip, batch_msm_mixed.hip,
-// fixed_bases.hip): the residency check of a lane kernel, the Straus table scratch, the chunk deal of a lane-set kernel and
+// batch_host.hpp -- the host launch path the batched-sum units share (batch_msm.hip, batch_msm_long.hip,
+// batch_msm_long_indexed.hip, batch_msm_mixed.hip, fixed_bases.hip): the residency check of a lane kernel, the Straus table scratch, the chunk deal of a lane-set kernel and
 // the frame of one device's slice of a host-pointer call.  (The fan-out over the devices is host_state.hpp's
 // slice_over_devices.)  Everything here runs under ctx->mu.
 #pragma once

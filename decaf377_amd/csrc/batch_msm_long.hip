@@ -16,7 +16,8 @@
 //
 // The chains write their partial sums as Element records (the double of the chain's result, as xyzt_out of the small sums)
 // and skip the compressor; the last fold level's records go through the chunked compressor with batched inversions
-// (codec_chunked.hip).  Everything below the host copy layer works on device pointers and a stream.
+// (codec_chunked.hip).  Everything below the host copy layer works on device pointers and a stream, and
+// d377_batch_long_msm[_encoded]_resident (include/decaf377_amd_long_sums.h) are that launch on the caller's buffers.
 //
 // A translation unit of its own, like batch_msm.hip: the register tables of the other units' kernels are measured artefacts.
 #include <hip/hip_runtime.h>
@@ -266,9 +267,10 @@ int batch_msm_long_one(DeviceState& d, bool encoded, const uint8_t* pts_in, cons
   });
 }
 
-// host pointers.  The checks come in the documented order -- m, null buffers (n > 0), ctx -- and before any device is touched.
-int batch_msm_long_host(d377_ctx* ctx, bool encoded, const void* pts_in, const uint8_t* scalars, size_t m, size_t n, uint8_t* out32,
-                        uint64_t* xyzt_out, uint8_t* status) {
+// What the host and the resident forms check first, in the documented order and before any device is touched: m, null
+// buffers (n > 0), ctx.
+int check_args(d377_ctx* ctx, bool encoded, const void* pts_in, const uint8_t* scalars, size_t m, size_t n, const uint8_t* out32,
+               const uint8_t* status) {
   if (m < 1 || m > BML_MAX)
     return fail_size(D377_ERR_ARG, "batch_msm_long: m = %zu: 1 .. 4096 terms per sum (D377_BATCH_MSM_LONG_MAX_TERMS); d377_msm for longer sums", m);
   if (n) {
@@ -278,6 +280,14 @@ int batch_msm_long_host(d377_ctx* ctx, bool encoded, const void* pts_in, const u
     if (encoded && !status) return fail(D377_ERR_ARG, "batch_msm_long: null buffer: %s", "status");
   }
   if (!ctx) return fail(D377_ERR_ARG, "%s", "batch_msm_long: null context (ctx)");
+  return D377_OK;
+}
+
+// host pointers
+int batch_msm_long_host(d377_ctx* ctx, bool encoded, const void* pts_in, const uint8_t* scalars, size_t m, size_t n, uint8_t* out32,
+                        uint64_t* xyzt_out, uint8_t* status) {
+  int rc;
+  if ((rc = check_args(ctx, encoded, pts_in, scalars, m, n, out32, status))) return rc;
   if (n == 0) return D377_OK;
   if (m <= BML_GROUP_MAX)                                     // one chain per sum: the small sums' call, the same bytes
     return encoded ? d377_batch_msm_small_encoded(ctx, (const uint8_t*)pts_in, scalars, m, n, out32, xyzt_out, status)
@@ -291,6 +301,26 @@ int batch_msm_long_host(d377_ctx* ctx, bool encoded, const void* pts_in, const u
   });
 }
 
+// device pointers and a stream (include/decaf377_amd_long_sums.h): the host form's checks, then dev and the alignment; enqueue
+// and return.  m <= 8 is the small sums' `_dev` call, as on the host; longer sums are batch_msm_long_launch under ctx->mu.
+int batch_msm_long_resident(d377_ctx* ctx, int dev, void* stream, bool encoded, const void* pts_in, const uint8_t* scalars, size_t m,
+                            size_t n, uint8_t* out32, uint64_t* xyzt_out, uint8_t* status) {
+  int rc;
+  if ((rc = check_args(ctx, encoded, pts_in, scalars, m, n, out32, status))) return rc;
+  if (dev < 0 || (size_t)dev >= ctx->devs.size()) return fail(D377_ERR_ARG, "%s", "batch_msm_long: dev is not a device of this context");
+  if (!aligned16(pts_in) || !aligned16(scalars) || !aligned16(out32) || !aligned16(xyzt_out))
+    return fail(D377_ERR_ARG, "%s", "batch_msm_long: device record buffers must be 16-byte aligned");
+  if (n == 0) return D377_OK;
+  if (m <= BML_GROUP_MAX)
+    return encoded ? d377_batch_msm_small_encoded_dev(ctx, dev, stream, (const uint8_t*)pts_in, scalars, m, n, out32, xyzt_out, status)
+                   : d377_batch_msm_small_dev(ctx, dev, stream, (const uint64_t*)pts_in, scalars, m, n, out32, xyzt_out);
+  if (n > SIZE_MAX / 128 / m) return fail(D377_ERR_ARG, "%s", "batch_msm_long: n x m overflows");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceState& d = ctx->devs[(size_t)dev];
+  HIP_TRY(hipSetDevice(d.id));
+  return batch_msm_long_launch(d, (hipStream_t)stream, encoded, pts_in, scalars, m, n, out32, xyzt_out, status);
+}
+
 }  // namespace
 
 extern "C" {
@@ -302,6 +332,14 @@ int d377_batch_msm_long(d377_ctx* ctx, const uint64_t* xyzt, const uint8_t* scal
 int d377_batch_msm_long_encoded(d377_ctx* ctx, const uint8_t* enc32, const uint8_t* scalar32, size_t m, size_t n, uint8_t* enc32_out,
                                 uint64_t* xyzt_out, uint8_t* status) {
   return batch_msm_long_host(ctx, true, enc32, scalar32, m, n, enc32_out, xyzt_out, status);
+}
+int d377_batch_long_msm_resident(d377_ctx* ctx, int dev, void* stream, const uint64_t* xyzt, const uint8_t* scalar32, size_t m, size_t n,
+                                 uint8_t* enc32_out, uint64_t* xyzt_out) {
+  return batch_msm_long_resident(ctx, dev, stream, false, xyzt, scalar32, m, n, enc32_out, xyzt_out, nullptr);
+}
+int d377_batch_long_msm_encoded_resident(d377_ctx* ctx, int dev, void* stream, const uint8_t* enc32, const uint8_t* scalar32, size_t m,
+                                         size_t n, uint8_t* enc32_out, uint64_t* xyzt_out, uint8_t* status) {
+  return batch_msm_long_resident(ctx, dev, stream, true, enc32, scalar32, m, n, enc32_out, xyzt_out, status);
 }
 
 }  // extern "C"

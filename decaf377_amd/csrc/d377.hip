@@ -1538,6 +1538,7 @@ void free_device(DeviceState& d) {
   if (d.pool_host) (void)hipHostFree(d.pool_host);
   d.pool_host = nullptr;
   for (int i = 0; i < 4; ++i) { (void)hipFree(d.buf[i]); (void)hipFree(d.buf2[i]); (void)hipFree(d.shard[i]); }
+  (void)hipFree(d.bmli_pool);
   for (int i = 0; i < 2; ++i) {
     if (d.ev_in[i]) (void)hipEventDestroy(d.ev_in[i]);
     if (d.ev_done[i]) (void)hipEventDestroy(d.ev_done[i]);

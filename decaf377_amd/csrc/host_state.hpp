@@ -114,6 +114,9 @@ struct DeviceState {
   uint8_t* bml_partials = nullptr;       // batch_msm_long.hip: the chains' partial sums and the fold levels' records; grown on demand, never shrunk
   size_t bml_cap = 0;
   int bml_lds[2] = {-1, -1};             // batch_msm_long.hip: LDS padding of its lane kernel (Element / Encoding form), -1 = not asked yet
+  int bmli_lds = -1;                     // batch_msm_long_indexed.hip: LDS padding of its lane kernel, -1 = not asked yet
+  uint8_t* bmli_pool = nullptr;          // batch_msm_long_indexed.hip: the pool's staging area of the host form; grown on demand
+  size_t bmli_pool_cap = 0;
   int fx_lds[4] = {-1, -1, -1, -1};      // fixed_bases.hip: LDS padding of its lane kernel per comb width (8 / 12 / 16 / 18), -1 = not asked yet
   int fxi_lds[4] = {-1, -1, -1, -1};     // the same for the lane kernel of the indexed sums
   int bmx_lds[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};   // batch_msm_mixed.hip: LDS padding of its lane kernel, [Element / Encoding form][comb width], -1 = not asked yet

@@ -1,6 +1,7 @@
-// straus_tab.hpp -- the device side the Straus-chain kernels share (batch_msm.hip, batch_msm_long.hip, batch_msm_mixed.hip
-// and no other unit): the per-lane table scratch of the lane kernels and the wave-per-sum chain.  Not part of straus.hpp,
-// which the host simulation compiles: the table is stored with slot_store.
+// straus_tab.hpp -- the device side the Straus-chain kernels share (batch_msm.hip, batch_msm_long.hip, batch_msm_mixed.hip;
+// batch_msm_long_indexed.hip takes StrausTab and keeps its own gathered copy of the wave chain): the per-lane table scratch of
+// the lane kernels and the wave-per-sum chain.  Not part of straus.hpp, which the host simulation compiles: the table is stored
+// with slot_store.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

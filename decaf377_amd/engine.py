@@ -83,6 +83,58 @@ def _check(a, spec, n, what, device=None):
         raise ValueError("%s: expected %s elements, got %s" % (what, "uint8" if kind == "u8" else "uint64/int64", a.dtype))
 
 
+# ---- what the resident routes of Context and FixedBases share
+def _on_device(dev, a):
+    """`a` as a contiguous tensor on `dev` (a numpy array or a tensor that lives elsewhere is copied there)."""
+    import torch
+    if not _is_torch(a):
+        a = np.ascontiguousarray(a)
+        a = torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a)
+    return a.detach().to(dev).contiguous()
+
+
+def _resident_outputs(what, dev, n, elements, status_rows=None, outs=None):
+    """The outputs of a resident call on `dev`: enc [n, 32], xyzt [n, 16] with elements, status [status_rows] for
+    Encodings -- allocated there, or the caller's `outs` in that order, checked like inputs."""
+    import torch
+    specs = [(ENC, n)] + ([(ELEM, n)] if elements else []) + ([(FLAG, status_rows)] if status_rows is not None else [])
+    if outs is None:
+        return [torch.empty((rows,) + tail, dtype=torch.uint8 if k == "u8" else torch.int64, device=dev) for (tail, k), rows in specs]
+    if len(outs) != len(specs):
+        raise ValueError("%s: %d output arrays expected" % (what, len(specs)))
+    for a, (spec, rows) in zip(outs, specs):
+        if not _is_torch(a):
+            raise ValueError(what + ": outs must be tensors on the inputs' device")
+        _check(a, spec, rows, what + " output", dev)
+        if not a.is_contiguous():
+            raise ValueError(what + " output must be contiguous")
+    return list(outs)
+
+
+def _resident_index(dev, index, what, arg):
+    """`index` as a contiguous [n, t] int32 tensor on `dev`; an int64 index outside 32 bits is the ValueError of the
+    host path (one synchronising reduction, for int64 tensors only)."""
+    import torch
+    idx = index if _is_torch(index) else torch.from_numpy(np.ascontiguousarray(index))
+    if idx.ndim != 2 or idx.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+        raise ValueError("%s: %s must be an [n, t] integer array" % (what, arg))
+    idx = idx.detach().to(dev)
+    if idx.dtype != torch.int32:
+        if idx.numel() and (int(idx.min()) < -(1 << 31) or int(idx.max()) >= (1 << 31)):
+            raise ValueError("%s: %s does not fit 32 bits" % (what, arg))
+        idx = idx.to(torch.int32)
+    return idx.contiguous()
+
+
+def _verdict_tensor(dev, n):
+    """The [2] int64 record a resident call writes; a call of no sums enqueues nothing, so its record is made here."""
+    import torch
+    verdict = torch.zeros((2,), dtype=torch.int64, device=dev)
+    if n == 0:
+        verdict[1] = -1
+    return verdict
+
+
 class Context:
     """Owns the device tables and scratch for one or more GPUs (d377_ctx)."""
 
@@ -538,8 +590,10 @@ class Context:
         points: [n * m, 16] u64 Elements or [n * m, 32] u8 Encodings (detected by the row width, as msm_small does),
         scalar32: [n * m, 32], term-major within a sum.  Returns what msm_small returns: enc [n, 32] for Elements, (enc,
         status [n * m]) for Encodings; with elements=True (enc, xyzt [n, 16]) / (enc, xyzt, status).  outs: the same tuple
-        of preallocated arrays.  The call is host-pointer only: torch tensors are staged through host memory (the results
-        come back on the points' device).  For ONE long sum use msm()."""
+        of preallocated arrays.  Tensors on a device of the context take d377_batch_long_msm[_encoded]_resident on torch's
+        current stream: no copy, no synchronisation, the results on that device.  numpy arrays keep the host-pointer call,
+        and tensors on a GPU the context does not own are staged through host memory (the results come back on the points'
+        device).  For ONE long sum use msm()."""
         m = int(m)
         if points.ndim != 2 or int(points.shape[1]) not in (16, 32):
             raise ValueError("msm_long: points must be [n * m, 16] Elements or [n * m, 32] Encodings")
@@ -555,9 +609,22 @@ class Context:
         if outs is not None and len(outs) != len(specs):
             raise ValueError("msm_long: %d output arrays expected" % len(specs))
         torch_in = _is_torch(points)
+        if torch_in and _cuda_device(self, points) is not None:    # resident: no copy, no synchronisation, torch's current stream
+            dev = points.device
+            di = self._dev_index(dev)
+            pts, sc = points.detach().contiguous(), scalar32.detach().contiguous()
+            res = _resident_outputs("msm_long", dev, n, elements, terms if encoded else None, outs)
+            p = lambda t: ctypes.c_void_p(t.data_ptr())
+            ptrs = [p(o) for o in res]
+            if not elements:
+                ptrs.insert(1, ctypes.c_void_p(None))
+            resident = self._lib.d377_batch_long_msm_encoded_resident if encoded else self._lib.d377_batch_long_msm_resident
+            _native.check(resident(self._h, di, _torch_stream(dev), p(pts), p(sc), ctypes.c_size_t(m), ctypes.c_size_t(n), *ptrs))
+            return tuple(res) if len(res) > 1 else res[0]
         if torch_in:
             dev = points.device
-            self._dev_index(dev)
+            if dev.type != "cuda":
+                self._dev_index(dev)                             # (raises: there is no CPU path for tensors)
             if outs is not None:
                 for a, (spec, rows) in zip(outs, specs):
                     _check(a, spec, rows, "msm_long output", dev)
@@ -583,6 +650,97 @@ class Context:
                 res = list(outs)
             return tuple(res) if len(res) > 1 else res[0]
         return tuple(host) if len(host) > 1 else host[0]
+
+    def msm_long_indexed(self, pool, point_index, scalar32, m, elements=False, check_indices=True, outs=None):
+        """n sums of m terms that name their points in a shared pool (d377_batch_long_msm_indexed):
+
+            out[i] = sum over j < m of scalars[i m + j] * pool[point_index[i, j]]
+
+        pool: [pool_count, 16] u64 Elements (a record with Z = 0 is the identity).  point_index: [n, m] int32 (int64 is
+        accepted and range-checked), each 0 .. pool_count-1, repeats allowed, or -1 for an absent term -- which costs as
+        much as a present one, so m is the longest sum's length; 1 <= m <= 4096 and m must equal point_index's second
+        dimension.  scalar32: [n * m, 32] or [n, m, 32] u8.  -> enc [n, 32] u8, or (enc, xyzt [n, 16]) with
+        elements=True.  Any other index raises NativeError and nothing is computed.
+        Routing is FixedBases.msm_indexed's: numpy arrays, CPU tensors and tensors on a GPU the context does not own take
+        the host-pointer call (sliced over the devices of a multi-GPU context, the pool sent to each).  When the pool, the
+        indices or the scalars are a tensor on a device of the context, the call runs on that one device: it is
+        d377_batch_long_msm_indexed_resident on torch's current stream (the other arguments are copied there if they live
+        elsewhere) and the results are allocated there.  check_indices=True first reduces the indices on the device and
+        reads the result -- the call's one synchronisation -- so that a refused index raises as above with no sum launched.
+        check_indices=False is fully asynchronous: the verdict tensor ([2] int64: the count of refused indices, the first
+        position or -1 = UINT64_MAX) is appended to the returned tuple, and a refused index has contributed nothing to its
+        sum.  outs: preallocated contiguous tensors on that device in the order of the result, without the verdict; the
+        host route allocates its own arrays and refuses outs with ValueError."""
+        what = "msm_long_indexed"
+        m = int(m)
+        if pool.ndim != 2 or int(pool.shape[1]) != 16:
+            raise ValueError(what + ": pool must be [pool_count, 16] Elements")
+        pool_count = _rows(pool)
+        _check(pool, ELEM, pool_count, what + " pool")
+        dev = _cuda_device(self, pool, point_index, scalar32)
+        if dev is not None:
+            di = self._dev_index(dev)
+            idx = _resident_index(dev, point_index, what, "point_index")
+            n = int(idx.shape[0])
+            if int(idx.shape[1]) != m:
+                raise ValueError(what + ": point_index must be [n, m]")
+            pl, sc = _on_device(dev, pool), _on_device(dev, scalar32)
+            if sc.ndim == 3:
+                if tuple(sc.shape[:2]) != (n, m):
+                    raise ValueError(what + ": scalars [n, m, 32] must match point_index [n, m]")
+                sc = sc.reshape(n * m, 32)
+            _check(sc, ENC, n * m, what + " scalars")
+            verdict = None
+            if check_indices:
+                flat = idx.reshape(-1)
+                bad = ((flat != -1) & ((flat < 0) | (flat >= pool_count))).nonzero()
+                if bad.numel():                                  # (the one synchronisation) the host form's text, restated
+                    first = int(bad[0])
+                    raise _native.error(-2, "d377_batch_long_msm_indexed: point_index[%d] = %d (sum %d, term %d) is neither -1 nor a "
+                                        "record 0 .. %d of the pool" % (first, int(flat[first]), first // m, first % m, pool_count - 1))
+            else:
+                verdict = _verdict_tensor(dev, n)
+            res = _resident_outputs(what, dev, n, elements, outs=outs)
+            p = lambda a: ctypes.c_void_p(a.data_ptr())
+            _native.check(self._lib.d377_batch_long_msm_indexed_resident(
+                self._h, di, _torch_stream(dev), p(pl), ctypes.c_size_t(pool_count), p(idx), p(sc), ctypes.c_size_t(m), ctypes.c_size_t(n),
+                p(res[0]), p(res[1]) if elements else None, p(verdict) if verdict is not None else None))
+            if verdict is not None:
+                res.append(verdict)
+            return tuple(res) if len(res) > 1 else res[0]
+        if outs is not None:
+            raise ValueError(what + ": outs goes with tensors on a device of the context")
+        tdev = next((a.device for a in (pool, point_index, scalar32) if _is_torch(a)), None)
+        host = lambda a: a.detach().cpu().numpy() if _is_torch(a) else a
+        idx = np.asarray(host(point_index))
+        if idx.ndim != 2 or idx.dtype.kind not in "iu":
+            raise ValueError(what + ": point_index must be an [n, m] integer array")
+        n = int(idx.shape[0])
+        if int(idx.shape[1]) != m:
+            raise ValueError(what + ": point_index must be [n, m]")
+        if idx.dtype != np.int32:
+            if idx.size and (int(idx.min()) < -(1 << 31) or int(idx.max()) >= (1 << 31)):
+                raise ValueError(what + ": point_index does not fit 32 bits")
+            idx = idx.astype(np.int32)
+        idx = np.ascontiguousarray(idx)
+        pl = np.ascontiguousarray(host(pool))
+        sc = np.ascontiguousarray(host(scalar32))
+        if sc.ndim == 3:
+            if sc.shape[:2] != (n, m):
+                raise ValueError(what + ": scalars [n, m, 32] must match point_index [n, m]")
+            sc = sc.reshape(n * m, 32)
+        _check(sc, ENC, n * m, what + " scalars")
+        enc = np.empty((n, 32), np.uint8)
+        xyzt = np.empty((n, 16), np.uint64) if elements else None
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _native.check(self._lib.d377_batch_long_msm_indexed(self._h, p(pl), ctypes.c_size_t(pool_count), p(idx), p(sc), ctypes.c_size_t(m),
+                                                            ctypes.c_size_t(n), p(enc), p(xyzt) if elements else None))
+        if tdev is not None:
+            import torch
+            enc = torch.from_numpy(enc).to(tdev)
+            if elements:
+                xyzt = torch.from_numpy(xyzt.view(np.int64)).to(tdev)
+        return (enc, xyzt) if elements else enc
 
     def msm(self, points, scalar32, encoded=None):
         """Element::vartime_multiscalar_mul (src/ark_curve/element/projective.rs:99-117).
@@ -712,29 +870,10 @@ class FixedBases:
         return int(g.value), int(b.value)
 
     def _on_device(self, dev, a):
-        """`a` as a contiguous tensor on `dev` (a numpy array or a tensor that lives elsewhere is copied there)."""
-        import torch
-        if not _is_torch(a):
-            a = np.ascontiguousarray(a)
-            a = torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a)
-        return a.detach().to(dev).contiguous()
+        return _on_device(dev, a)
 
     def _outputs(self, what, dev, n, elements, status_rows=None, outs=None):
-        """The outputs of a resident call on `dev`: enc [n, 32], xyzt [n, 16] with elements, status [status_rows] for
-        Encodings -- allocated there, or the caller's `outs` in that order, checked like inputs."""
-        import torch
-        specs = [(ENC, n)] + ([(ELEM, n)] if elements else []) + ([(FLAG, status_rows)] if status_rows is not None else [])
-        if outs is None:
-            return [torch.empty((rows,) + tail, dtype=torch.uint8 if k == "u8" else torch.int64, device=dev) for (tail, k), rows in specs]
-        if len(outs) != len(specs):
-            raise ValueError("%s: %d output arrays expected" % (what, len(specs)))
-        for a, (spec, rows) in zip(outs, specs):
-            if not _is_torch(a):
-                raise ValueError(what + ": outs must be tensors on the inputs' device")
-            _check(a, spec, rows, what + " output", dev)
-            if not a.is_contiguous():
-                raise ValueError(what + " output must be contiguous")
-        return list(outs)
+        return _resident_outputs(what, dev, n, elements, status_rows, outs)
 
     def _dense(self, symbol, what, scalar32, elements):
         h = self._live()
@@ -771,27 +910,11 @@ class FixedBases:
         return (enc, xyzt) if elements else enc
 
     def _resident_index(self, dev, base_index, what):
-        """base_index as a contiguous [n, t] int32 tensor on `dev`; an int64 index outside 32 bits is the ValueError of the
-        host path (one synchronising reduction, for int64 tensors only)."""
-        import torch
-        idx = base_index if _is_torch(base_index) else torch.from_numpy(np.ascontiguousarray(base_index))
-        if idx.ndim != 2 or idx.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
-            raise ValueError(what + ": base_index must be an [n, t] integer array")
-        idx = idx.detach().to(dev)
-        if idx.dtype != torch.int32:
-            if idx.numel() and (int(idx.min()) < -(1 << 31) or int(idx.max()) >= (1 << 31)):
-                raise ValueError(what + ": base_index does not fit 32 bits")
-            idx = idx.to(torch.int32)
-        return idx.contiguous()
+        return _resident_index(dev, base_index, what, "base_index")
 
     @staticmethod
     def _verdict_tensor(dev, n):
-        """The [2] int64 record a resident call writes; a call of no sums enqueues nothing, so its record is made here."""
-        import torch
-        verdict = torch.zeros((2,), dtype=torch.int64, device=dev)
-        if n == 0:
-            verdict[1] = -1
-        return verdict
+        return _verdict_tensor(dev, n)
 
     def _verdict(self, dev, di, idx, symbol):
         """check_indices=True: d377_check_base_index_resident, then the one synchronisation -- the 16-byte record is read, and on

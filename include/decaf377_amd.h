@@ -324,8 +324,8 @@ int d377_batch_msm_small_encoded(d377_ctx* ctx, const uint8_t* enc32, const uint
  * allocation is D377_ERR_HIP and leaves nothing half-allocated).
  * Arguments are checked in this order, the first two before any device is touched: m (0 or more than 4096 is D377_ERR_ARG,
  * the message names m), null buffers when n > 0, ctx; n == 0 with good arguments is D377_OK.  A multi-GPU context slices the
- * SUMS over its devices.  Host pointers only: a device-pointer form is not offered (a Python torch tensor is staged through
- * host memory). */
+ * SUMS over its devices.  Device buffers take d377_batch_long_msm[_encoded]_resident, and sums whose terms name their points
+ * in a shared pool d377_batch_long_msm_indexed[_resident]: decaf377_amd_long_sums.h, which this header includes at its end. */
 #define D377_BATCH_MSM_LONG_MAX_TERMS 4096
 int d377_batch_msm_long(d377_ctx* ctx, const uint64_t* xyzt, const uint8_t* scalar32, size_t m, size_t n, uint8_t* enc32_out,
                         uint64_t* xyzt_out);
@@ -601,5 +601,6 @@ int d377_batch_sharded_dev(d377_ctx* ctx, int root_dev, void* stream, int op, co
 #endif
 
 #include "decaf377_amd_resident.h"
+#include "decaf377_amd_long_sums.h"
 
 #endif /* DECAF377_AMD_H */

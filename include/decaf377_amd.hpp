@@ -531,6 +531,38 @@ class Engine {
     if (encodings) *encodings = std::move(enc);
     return {out, results(points, st)};
   }
+  /// Long sums whose terms name their points in a shared pool (d377_batch_long_msm_indexed): sum i = sum over j < m of
+  /// scalars[i m + j] * pool[point_index[i m + j]], -1 an absent term.  Any other index outside the pool throws and nothing
+  /// is computed.
+  std::vector<Element> vartime_multiscalar_mul_batch_long_indexed(size_t m, const std::vector<Element>& pool, const std::vector<int>& point_index,
+                                                                  const std::vector<Fr>& scalars, std::vector<Encoding>* encodings = nullptr) {
+    if (scalars.size() != point_index.size() || m == 0 || point_index.size() % m) throw std::invalid_argument("length mismatch");
+    std::vector<Element> out(point_index.size() / m);
+    std::vector<Encoding> enc(out.size());
+    check(d377_batch_long_msm_indexed(ctx_, u64(pool), pool.size(), point_index.data(), u8(scalars), m, out.size(), u8m(enc),
+                                      reinterpret_cast<uint64_t*>(out.data())));
+    if (encodings) *encodings = std::move(enc);
+    return out;
+  }
+  /// The resident forms of the long sums (decaf377_amd_long_sums.h): every pointer is a DEVICE pointer on device `dev` of the
+  /// Engine (records 16-byte aligned), the call enqueues on `stream` and returns.  elements_out and verdict may be null; an
+  /// index outside the pool contributes nothing and is counted in `verdict` (two u64: the count, the first position).
+  void msm_long_resident(int dev, void* stream, const Element* points, const Fr* scalars, size_t m, size_t n, Encoding* enc_out,
+                         Element* elements_out = nullptr) {
+    check(d377_batch_long_msm_resident(ctx_, dev, stream, reinterpret_cast<const uint64_t*>(points), reinterpret_cast<const uint8_t*>(scalars), m, n,
+                                       reinterpret_cast<uint8_t*>(enc_out), reinterpret_cast<uint64_t*>(elements_out)));
+  }
+  void msm_long_resident(int dev, void* stream, const Encoding* points, const Fr* scalars, size_t m, size_t n, Encoding* enc_out,
+                         Element* elements_out, uint8_t* status) {
+    check(d377_batch_long_msm_encoded_resident(ctx_, dev, stream, reinterpret_cast<const uint8_t*>(points), reinterpret_cast<const uint8_t*>(scalars),
+                                               m, n, reinterpret_cast<uint8_t*>(enc_out), reinterpret_cast<uint64_t*>(elements_out), status));
+  }
+  void msm_long_indexed_resident(int dev, void* stream, const Element* pool, size_t pool_count, const int* point_index, const Fr* scalars,
+                                 size_t m, size_t n, Encoding* enc_out, Element* elements_out = nullptr, uint64_t* verdict = nullptr) {
+    check(d377_batch_long_msm_indexed_resident(ctx_, dev, stream, reinterpret_cast<const uint64_t*>(pool), pool_count, point_index,
+                                               reinterpret_cast<const uint8_t*>(scalars), m, n, reinterpret_cast<uint8_t*>(enc_out),
+                                               reinterpret_cast<uint64_t*>(elements_out), verdict));
+  }
   /// CurveGroup::normalize_batch (src/ark_curve/element.rs:74-81): affine (x, y) as 4 Montgomery limbs each
   std::vector<std::array<uint64_t, 8>> normalize_batch(const std::vector<Element>& p) {
     std::vector<std::array<uint64_t, 8>> out(p.size());

@@ -32,7 +32,7 @@ extern "C" {
  * replay that contains these calls must NOT overlap another batched-sum call of the same device on a different stream: the
  * table scratch's layout depends on the term count, and a capturing stream takes no part in the hand-over by events (order
  * them with the same stream or your own events).  Destroying a handle that a captured graph still names is the caller's
- * error.  The long variable-base sums (d377_batch_msm_long) have no resident form.
+ * error.  The long variable-base sums' resident forms are in decaf377_amd_long_sums.h, under this contract.
  *
  * The index verdict.  The host forms of the indexed and mixed sums read every index before any launch; a resident call
  * cannot without a synchronisation.  Instead, when verdict != NULL, a small kernel in front of the sums kernel writes ONE

@@ -36,6 +36,8 @@ use crate::{Element, Encoding, EncodingError, Fq, Fr};
 pub mod ffi;
 #[path = "gpu/ffi_resident.rs"]
 pub mod ffi_resident;                                             // rust/src/ffi_resident.rs, from include/decaf377_amd_resident.h
+#[path = "gpu/ffi_long_sums.rs"]
+pub mod ffi_long_sums;                                            // rust/src/ffi_long_sums.rs, from include/decaf377_amd_long_sums.h
 
 /// Which backend's root `sqrt_ratio_zeta_batch` returns (the flags are the same).
 #[derive(Copy, Clone, Debug, PartialEq, Eq)]
@@ -548,6 +550,23 @@ impl Element {
         })?;
         Ok((out.chunks_exact(16).map(element_from_xyzt).collect(), enc, results(&st, |_| ())))
     }
+    /// Long sums whose terms name their points: sum i = sum over j < m of scalars[i m + j] * pool[point_index[i m + j]]
+    /// (d377_batch_long_msm_indexed).  -1 is an absent term; any other index outside the pool is refused before any launch.
+    pub fn vartime_multiscalar_mul_batch_long_indexed_gpu(ctx: &GpuContext, m: usize, pool: &[Element], point_index: &[i32], scalars: &[Fr])
+        -> Result<(Vec<Element>, Vec<Encoding>), GpuError> {
+        assert_eq!(scalars.len(), point_index.len());
+        assert!(m >= 1 && point_index.len() % m == 0);
+        let n = point_index.len() / m;
+        let xyzt = elements_to_xyzt(pool);
+        let bytes = pack32(scalars, |k| k.to_bytes());
+        let mut enc = vec![Encoding([0u8; 32]); n];
+        let mut out = vec![0u64; 16 * n];
+        check(unsafe {
+            ffi_long_sums::d377_batch_long_msm_indexed(ctx.0, xyzt.as_ptr(), pool.len(), point_index.as_ptr(), bytes.as_ptr(), m, n,
+                                                       enc.as_mut_ptr() as *mut u8, out.as_mut_ptr())
+        })?;
+        Ok((out.chunks_exact(16).map(element_from_xyzt).collect(), enc))
+    }
 }
 
 // ---- Fq / Fr -----------------------------------------------------------------------------------
@@ -744,5 +763,22 @@ pub mod dev {
     pub unsafe fn check_base_index_resident(fb: &FixedBases, dev: i32, stream: *mut c_void, base_index: *const i32, count: usize,
                                             verdict: *mut u64) -> Result<(), GpuError> {
         check(ffi_resident::d377_check_base_index_resident(fb.ctx.0, dev, stream, fb.handle, base_index, count, verdict))
+    }
+
+    // The long variable-base sums on device buffers and over a pool (ffi_long_sums.rs): `xyzt_out` and `verdict` may be null; an
+    // index outside the pool contributes nothing and is counted in `verdict`, as above.
+    pub unsafe fn msm_long_resident(ctx: &GpuContext, dev: i32, stream: *mut c_void, xyzt: *const u64, scalar32: *const u8, m: usize, n: usize,
+                                    enc32_out: *mut u8, xyzt_out: *mut u64) -> Result<(), GpuError> {
+        check(ffi_long_sums::d377_batch_long_msm_resident(ctx.0, dev, stream, xyzt, scalar32, m, n, enc32_out, xyzt_out))
+    }
+    pub unsafe fn msm_long_encoded_resident(ctx: &GpuContext, dev: i32, stream: *mut c_void, enc32: *const u8, scalar32: *const u8, m: usize,
+                                            n: usize, enc32_out: *mut u8, xyzt_out: *mut u64, status: *mut u8) -> Result<(), GpuError> {
+        check(ffi_long_sums::d377_batch_long_msm_encoded_resident(ctx.0, dev, stream, enc32, scalar32, m, n, enc32_out, xyzt_out, status))
+    }
+    pub unsafe fn msm_long_indexed_resident(ctx: &GpuContext, dev: i32, stream: *mut c_void, pool_xyzt: *const u64, pool_count: usize,
+                                            point_index: *const i32, scalar32: *const u8, m: usize, n: usize, enc32_out: *mut u8,
+                                            xyzt_out: *mut u64, verdict: *mut u64) -> Result<(), GpuError> {
+        check(ffi_long_sums::d377_batch_long_msm_indexed_resident(ctx.0, dev, stream, pool_xyzt, pool_count, point_index, scalar32, m, n,
+                                                                  enc32_out, xyzt_out, verdict))
     }
 }
