@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI declared in include/decaf377_amd.h (and decaf377_amd_resident.h and decaf377_amd_long_sums.h, which it includes).
+"""ctypes binding of the C ABI declared in include/decaf377_amd.h (and decaf377_amd_resident.h, decaf377_amd_long_sums.h and
+decaf377_amd_bucket_sums.h, which it includes).
 
 The shared library is built in-tree by `__graft_entry__.build()` (hipcc, gfx950) as
 decaf377_amd/lib/libdecaf377_amd.so.  There is no CPU fallback: if the library is missing
@@ -55,6 +56,11 @@ RESIDENT_EXPORTS = [
 LONG_SUMS_EXPORTS = [
     "d377_batch_long_msm_resident", "d377_batch_long_msm_encoded_resident", "d377_batch_long_msm_indexed",
     "d377_batch_long_msm_indexed_resident",
+]
+# every symbol include/decaf377_amd_bucket_sums.h declares (checked by tests/test_bucket_sums_host.py)
+BUCKET_SUMS_EXPORTS = [
+    "d377_batch_bucket_msm", "d377_batch_bucket_msm_encoded", "d377_batch_bucket_msm_resident",
+    "d377_batch_bucket_msm_encoded_resident", "d377_bucket_msm_plan",
 ]
 
 
@@ -237,6 +243,15 @@ def load():
         "d377_batch_long_msm_encoded_resident": [vp, i32, vp, vp, vp, sz, sz, vp, vp, vp],
         "d377_batch_long_msm_indexed": [vp, vp, sz, vp, vp, sz, sz, vp, vp],
         "d377_batch_long_msm_indexed_resident": [vp, i32, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp],
+    })
+    # many sums by buckets (decaf377_amd_bucket_sums.h): host forms, resident forms, the plan
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    resident.update({
+        "d377_batch_bucket_msm": [vp, vp, vp, sz, sz, i32, vp, vp],
+        "d377_batch_bucket_msm_encoded": [vp, vp, vp, sz, sz, i32, vp, vp, vp],
+        "d377_batch_bucket_msm_resident": [vp, i32, vp, vp, vp, sz, sz, i32, vp, vp],
+        "d377_batch_bucket_msm_encoded_resident": [vp, i32, vp, vp, vp, sz, sz, i32, vp, vp, vp],
+        "d377_bucket_msm_plan": [vp, i32, sz, sz, i32, ctypes.POINTER(i32), u64p, u64p, u64p],
     })
     for name, args in resident.items():
         getattr(lib, name).argtypes = args

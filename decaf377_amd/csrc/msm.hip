@@ -1586,15 +1586,13 @@ struct MsmCall { DeviceState& d; hipStream_t s; const MsmPlan& p; size_t n; };
 template <class T = uint32_t>
 T* msm_at(const MsmCall& c, MsmRegion r) { return reinterpret_cast<T*>(c.d.msm.mem + c.p.region[r].offset); }
 
-// Phase 1: prepare (points -> affine records, scalars -> digits) and the counting pass, for the digit type of this window width
+// Phase 1: prepare (points -> affine records, scalars -> digits, written to `dig`) and the counting pass, for the digit type of
+// this window width
 template <class DT>
-int msm_prepare_count(const MsmCall& c, bool encoded, const void* pts_in, const uint8_t* scalars, uint8_t* status) {
+int msm_prepare(const MsmCall& c, bool encoded, const void* pts_in, const uint8_t* scalars, uint8_t* status, DT* dig) {
   DeviceState& d = c.d; const MsmPlan& p = c.p; const hipStream_t s = c.s; const size_t n = c.n;
   const SqrtTables T = d.tables();
   uint32_t* pts = msm_at(c, R_PTS);
-  DT* dig = msm_at<DT>(c, R_DIGITS);
-  if (p.hist_bytes > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_count<DT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.hist_bytes));
   if (n) {
     if (encoded) {
       const size_t chunked_min = (size_t)d.tuned(D377_TUNE_MSM_ENC_CHUNKED_MIN, (long long)(d.resident_lanes() * DCB_ASSIST_MIN));
@@ -1632,9 +1630,22 @@ int msm_prepare_count(const MsmCall& c, bool encoded, const void* pts_in, const 
                          scalars, n, p.shape, pts, dig, zflag);
     }
   }
-  hipLaunchKernelGGL(k_msm_count<DT>, dim3(p.W * p.S * p.count_parts), dim3(SORT_THREADS), p.hist_bytes, s, dig, n, p.nb, p.S, p.per, p.count_parts,
-                     p.count_nbr, msm_at(c, R_BLOCKHIST));
   return D377_OK;
+}
+template <class DT>
+int msm_count(const MsmCall& c) {
+  const MsmPlan& p = c.p;
+  if (p.hist_bytes > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_count<DT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.hist_bytes));
+  hipLaunchKernelGGL(k_msm_count<DT>, dim3(p.W * p.S * p.count_parts), dim3(SORT_THREADS), p.hist_bytes, c.s, msm_at<const DT>(c, R_DIGITS), c.n, p.nb, p.S,
+                     p.per, p.count_parts, p.count_nbr, msm_at(c, R_BLOCKHIST));
+  return D377_OK;
+}
+template <class DT>
+int msm_prepare_count(const MsmCall& c, bool encoded, const void* pts_in, const uint8_t* scalars, uint8_t* status) {
+  int rc;
+  if ((rc = msm_prepare<DT>(c, encoded, pts_in, scalars, status, msm_at<DT>(c, R_DIGITS)))) return rc;
+  return msm_count<DT>(c);
 }
 
 // Phase 2: the scans (bucket offsets, L, the plan of the bucket sums) and the two placement levels of the sort (TileLds: 73 KiB
@@ -1667,8 +1678,9 @@ int msm_scan_place(const MsmCall& c) {
   return p.packed ? msm_place<true, int16_t>(c) : msm_place<false, int16_t>(c);
 }
 
-// Phase 3: the span sums, the reduction levels, the buckets, the weighted sums per window and the final Horner chain
-int msm_sums(const MsmCall& c, uint8_t* enc_out, uint64_t* xyzt_out) {
+// Phase 3: the span sums, the reduction levels and the buckets (msm_bucket_records: R_BUCKETS holds [W][nb] records after it),
+// then the weighted sums per window and the final Horner chain
+int msm_bucket_records(const MsmCall& c) {
   DeviceState& d = c.d; const MsmPlan& p = c.p; const hipStream_t s = c.s;
   const int W = p.W, nb = p.nb;
   uint32_t *segoff = msm_at(c, R_SEGOFF), *lvlmax = msm_at(c, R_LVLMAX), *meta = msm_at(c, R_META), *bkt = msm_at(c, R_BUCKETS);
@@ -1693,6 +1705,14 @@ int msm_sums(const MsmCall& c, uint8_t* enc_out, uint64_t* xyzt_out) {
     hipLaunchKernelGGL(k_msm_buckets<1>, dim3(grid_of(d, (size_t)W * nb)), dim3(BLOCK), 0, s, lv, sp, segoff, lvlmax, p.red.skip, W, nb, bkt, meta);
   else
     hipLaunchKernelGGL(k_msm_buckets<2>, dim3(grid_of(d, (size_t)W * nb * 2)), dim3(BLOCK), 0, s, lv, sp, segoff, lvlmax, p.red.skip, W, nb, bkt, meta);
+  return D377_OK;
+}
+int msm_sums(const MsmCall& c, uint8_t* enc_out, uint64_t* xyzt_out) {
+  DeviceState& d = c.d; const MsmPlan& p = c.p; const hipStream_t s = c.s;
+  const int W = p.W, nb = p.nb;
+  int rc;
+  if ((rc = msm_bucket_records(c))) return rc;
+  uint32_t* bkt = msm_at(c, R_BUCKETS);
   const uint32_t* cur_in;
   if (p.tree) {
     uint32_t *nodes = msm_at(c, R_NODES), *sums = msm_at(c, R_SUMS);
@@ -1726,6 +1746,17 @@ int msm_sums(const MsmCall& c, uint8_t* enc_out, uint64_t* xyzt_out) {
   return D377_OK;
 }
 
+// Lanes of the span sums (k_msm_spans): as many as the device keeps resident at once -- what the runtime says the kernel's
+// registers allow (4 workgroups per CU at 128 VGPRs: tests/test_codegen.py), asked once per device -> d.msm_span_blocks.
+int msm_span_blocks(DeviceState& d) {
+  if (d.msm_span_blocks < 0) {
+    int nblk = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, reinterpret_cast<const void*>(k_msm_spans), BLOCK, 0));
+    d.msm_span_blocks = nblk < 1 ? 1 : (nblk > SEG_BLOCKS_PER_CU ? SEG_BLOCKS_PER_CU : nblk);
+  }
+  return D377_OK;
+}
+
 // everything on device pointers, enqueued on `s`
 int msm_launch(DeviceState& d, hipStream_t s, bool encoded, const void* pts_in, const uint8_t* scalars, size_t n,
                uint8_t* enc_out, uint64_t* xyzt_out, uint8_t* status) {
@@ -1733,19 +1764,13 @@ int msm_launch(DeviceState& d, hipStream_t s, bool encoded, const void* pts_in, 
   if (n && n <= msm_small_max(d, encoded) && n < ((size_t)1 << 24)) return msm_launch_small(d, s, encoded, pts_in, scalars, n, enc_out, xyzt_out, status);
   MsmPlanIn in;
   in.n = n; in.c = pick_window(d, n); in.cus = d.cus;
-  // Lanes of the span sums (k_msm_spans): as many as the device keeps resident at once -- what the runtime says the kernel's
-  // registers allow (4 workgroups per CU at 128 VGPRs: tests/test_codegen.py), asked once per device.
-  if (d.msm_span_blocks < 0) {
-    int nblk = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, reinterpret_cast<const void*>(k_msm_spans), BLOCK, 0));
-    d.msm_span_blocks = nblk < 1 ? 1 : (nblk > SEG_BLOCKS_PER_CU ? SEG_BLOCKS_PER_CU : nblk);
-  }
+  int rc;
+  if ((rc = msm_span_blocks(d))) return rc;
   in.span_blocks = d.msm_span_blocks;
   in.slices = d.tuned(D377_TUNE_MSM_SLICES, PLAN_DEFAULT); in.seg = d.tuned(D377_TUNE_MSM_SEG, PLAN_DEFAULT);   // developer overrides (sweeps)
   in.red = d.tuned(D377_TUNE_MSM_RED, PLAN_DEFAULT); in.skip = d.tuned(D377_TUNE_MSM_SKIP, PLAN_DEFAULT);
   in.chunked_sums = d.tuned(D377_TUNE_MSM_CHUNKED_SUMS, PLAN_DEFAULT); in.sort_packed = d.tuned(D377_TUNE_MSM_SORT_PACKED, PLAN_DEFAULT);
   const MsmPlan p = msm_plan(in);
-  int rc;
   MsmHeld held{d.msm.guard, s, false};
   if ((rc = msm_reserve(d, s, p.bytes, held))) return rc;
   const MsmCall call{d, s, p, n};
@@ -1896,3 +1921,6 @@ int d377_sum_elements_dev(d377_ctx* ctx, int dev, void* stream, const uint64_t* 
 }
 
 }  // extern "C"
+
+// d377_batch_bucket_msm: many sums through one run of the pipeline above per pass (kernels, launcher, C entry points)
+#include "msm_batch.inc"

@@ -122,9 +122,13 @@ struct MsmPlanIn {
   int c, cus, span_blocks;               // window width (msm.hip: pick_window), CUs, workgroups of k_msm_spans a CU holds (occupancy query)
   // the developer overrides D377_TUNE_MSM_SLICES, _SEG, _RED, _SKIP, _CHUNKED_SUMS, _SORT_PACKED
   long long slices = PLAN_DEFAULT, seg = PLAN_DEFAULT, red = PLAN_DEFAULT, skip = PLAN_DEFAULT, chunked_sums = PLAN_DEFAULT, sort_packed = PLAN_DEFAULT;
+  // SUMS that share the pipeline (msm_batch_plan.hpp): n points, n / sums per sum, under composite bucket keys -- sum k owns the
+  // buckets k 2^(c-1) + 1 .. (k + 1) 2^(c-1) of every window.  One sum (the default) is d377_msm's plan, unchanged.
+  size_t sums = 1;
 };
 struct MsmPlan {
-  WinShape shape; int W, nb;             // the windows; bucket indices 0 .. 2^(c-1)
+  WinShape shape; int W, nb;             // the windows; bucket indices 0 .. sums * 2^(c-1)
+  size_t sums; int pw;                   // sums that share the buckets; pseudo-windows W * sums: the tree's windows, 2^(c-1) leaves each
   int S; size_t per;                     // slices per window of the counting sort, points per slice
   bool wide_digits;                      // |digit| <= 2^(c-1): int16 up to 16-bit windows, int32 beyond
   int count_parts, count_nbr; size_t hist_bytes;     // the counting pass: parts per window, buckets per part, its LDS histogram
@@ -149,7 +153,9 @@ inline MsmPlan msm_plan(const MsmPlanIn& in) {
   const size_t n = in.n; const int c = in.c;
   p.shape = win_shape(c);                                      // W windows of c or c - 1 bits that tile the 252 scalar bits
   const int W = p.W = p.shape.W;
-  const int nb = p.nb = (1 << (c - 1)) + 1;
+  const size_t K = p.sums = in.sums < 1 ? 1 : in.sums;         // (msm_batch_plan.hpp keeps K 2^(c-1) within the sort's 2^17)
+  const int nb = p.nb = (int)(K << (c - 1)) + 1;
+  const int PW = p.pw = W * (int)K;
   // slices per window of the counting sort: enough workgroups to cover the chip, never less than 8192 points each
   // (W * S <= the 2 workgroups of 1024 threads a CU holds: with one more slice per window, 18 x 29 = 522 workgroups on 512
   // places, the count and level-1 placement kernels ran a second generation for ten workgroups)
@@ -157,7 +163,7 @@ inline MsmPlan msm_plan(const MsmPlanIn& in) {
   if ((size_t)S > (n + 8191) / 8192) S = (int)((n + 8191) / 8192);
   if (S < 1) S = 1;
   p.S = S; p.per = (n + (size_t)S - 1) / (size_t)S;
-  p.wide_digits = c > 16;
+  p.wide_digits = nb - 1 > (1 << 15);                          // one sum: c > 16
   // the counting pass keeps a histogram of at most 2^15 + 1 buckets in LDS (128 KiB): wider windows are counted in parts
   p.count_parts = (nb + (1 << 15)) / ((1 << 15) + 1);
   p.count_nbr = (nb + p.count_parts - 1) / p.count_parts;
@@ -194,8 +200,8 @@ inline MsmPlan msm_plan(const MsmPlanIn& in) {
   }
   // weighted bucket sums by the pairwise tree (every width); the chunked running sums remain as a developer override
   // (D377_TUNE_MSM_CHUNKED_SUMS), the tree's cross-check
-  p.tree = tuned(in.chunked_sums, 0) == 0;
-  // the tree's leaves are buckets 1 .. 2^(c-1) (bucket 0 is empty): depth c - 1, a whole number of blocks
+  p.tree = tuned(in.chunked_sums, 0) == 0 || K > 1;           // (several sums: the tree alone knows pseudo-windows)
+  // the tree's leaves are buckets 1 .. 2^(c-1) (bucket 0 is empty) of each sum: depth c - 1, a whole number of blocks
   const int depth = p.ws_depth = c - 1;
   // trees deeper than 15 (17- and 18-bit windows): a middle level merges the block nodes 8 or 16 to 1 (k_msm_wsum_mid), down
   // to 16 nodes per window for k_msm_wsum_window
@@ -205,11 +211,11 @@ inline MsmPlan msm_plan(const MsmPlanIn& in) {
   // CU.  And always under the middle level, whose LDS buffers (WSM_CAP) hold the first level of its 8- or 16-to-1 merge of
   // 9-deep nodes and not that of 8-deep ones.  The CU-count rule alone says the same below 1280 CUs (c = 17: W = 15 and
   // 15 * 2^8 > 3 * cus; c = 18: below 2390 CUs; an MI355X has 256), so the second clause changes nothing on today's devices.
-  const bool ws8 = depth >= WS_M8 && ((size_t)W * ((size_t)1 << (depth - WS_M)) > (size_t)in.cus * 3 || p.ws_mid);
+  const bool ws8 = depth >= WS_M8 && ((size_t)PW * ((size_t)1 << (depth - WS_M)) > (size_t)in.cus * 3 || p.ws_mid);
   p.ws_m = ws8 ? WS_M8 : (depth < WS_M ? depth : WS_M);        // >= 2: window widths start at 4 here
   p.ws_nblk = 1 << (depth - p.ws_m);
   p.block_kernel = ws8 ? WSUM_BLOCK8
-                       : ((size_t)2 * W * p.ws_nblk <= (size_t)in.cus * 4 ? WSUM_BLOCK2 : WSUM_BLOCK);   // two waves per block while every wave keeps its own SIMD
+                       : ((size_t)2 * PW * p.ws_nblk <= (size_t)in.cus * 4 ? WSUM_BLOCK2 : WSUM_BLOCK);   // two waves per block while every wave keeps its own SIMD
   if (p.tree) {
     p.top_m = p.ws_mid ? p.mid_m : p.ws_m; p.top_nblk = p.ws_mid ? p.mid_nblk : p.ws_nblk; p.top_stride = p.ws_mid ? MID_STRIDE : NODE_STRIDE;
     p.cap0 = wsb_cap0(depth, p.top_m); p.cap1 = wsb_cap1(depth, p.top_m);
@@ -240,12 +246,12 @@ inline MsmPlan msm_plan(const MsmPlanIn& in) {
   bytes[R_BUCKETS] = (size_t)W * nb * PT_WORDS * 4;
   for (int l = 1; l < REDUCE_LEVELS; ++l) bytes[R_RED1 + l - 1] = p.max_g[l] * PT_WORDS * 4;
   bytes[R_LVLMAX] = LVL_WORDS * sizeof(uint32_t);
-  bytes[R_CHUNKS] = (size_t)W * p.nchunks * PT_WORDS * 4;
-  bytes[R_FOLD0] = (size_t)W * m1 * PT_WORDS * 4;
-  bytes[R_FOLD1] = (size_t)W * m2 * PT_WORDS * 4;
-  bytes[R_NODES] = p.tree ? (size_t)W * p.ws_nblk * NODE_STRIDE * PT_WORDS * 4 : 0;
+  bytes[R_CHUNKS] = K > 1 ? 0 : (size_t)W * p.nchunks * PT_WORDS * 4;
+  bytes[R_FOLD0] = K > 1 ? 0 : (size_t)W * m1 * PT_WORDS * 4;
+  bytes[R_FOLD1] = K > 1 ? 0 : (size_t)W * m2 * PT_WORDS * 4;
+  bytes[R_NODES] = p.tree ? (size_t)PW * p.ws_nblk * NODE_STRIDE * PT_WORDS * 4 : 0;
   bytes[R_MID] = p.ws_mid ? (size_t)W * p.mid_nblk * MID_STRIDE * PT_WORDS * 4 : 0;
-  bytes[R_SUMS] = (size_t)W * PT_WORDS * 4;
+  bytes[R_SUMS] = (size_t)PW * PT_WORDS * 4;
   size_t off = 0;
   for (int r = 0; r < R_COUNT; ++r) {
     p.region[r] = MsmSpan{off, bytes[r]};

@@ -594,32 +594,38 @@ class Context:
         current stream: no copy, no synchronisation, the results on that device.  numpy arrays keep the host-pointer call,
         and tensors on a GPU the context does not own are staged through host memory (the results come back on the points'
         device).  For ONE long sum use msm()."""
+        return self._sums_of_m("msm_long", ("d377_batch_msm_long", "d377_batch_msm_long_encoded"),
+                               ("d377_batch_long_msm_resident", "d377_batch_long_msm_encoded_resident"), points, scalar32, m, outs, elements)
+
+    def _sums_of_m(self, what, host_names, resident_names, points, scalar32, m, outs, elements, extra=()):
+        """What msm_long and msm_buckets share: n sums of m terms, host or resident by where the points live; `extra`: the
+        call's own arguments between n and the outputs."""
         m = int(m)
         if points.ndim != 2 or int(points.shape[1]) not in (16, 32):
-            raise ValueError("msm_long: points must be [n * m, 16] Elements or [n * m, 32] Encodings")
+            raise ValueError("%s: " % what + "points must be [n * m, 16] Elements or [n * m, 32] Encodings")
         encoded = int(points.shape[1]) == 32
         terms = _rows(points)
         if m < 1 or terms % m:
-            raise ValueError("msm_long: the number of points must be a multiple of m")
+            raise ValueError("%s: " % what + "the number of points must be a multiple of m")
         n = terms // m
-        _check(points, ENC if encoded else ELEM, terms, "msm_long points")
-        _check(scalar32, ENC, terms, "msm_long scalars", points.device if _is_torch(points) else None)
-        name = "d377_batch_msm_long_encoded" if encoded else "d377_batch_msm_long"
+        _check(points, ENC if encoded else ELEM, terms, what + " points")
+        _check(scalar32, ENC, terms, what + " scalars", points.device if _is_torch(points) else None)
+        name = host_names[1 if encoded else 0]
         specs = [(ENC, n)] + ([(ELEM, n)] if elements else []) + ([(FLAG, terms)] if encoded else [])
         if outs is not None and len(outs) != len(specs):
-            raise ValueError("msm_long: %d output arrays expected" % len(specs))
+            raise ValueError("%s: " % what + "%d output arrays expected" % len(specs))
         torch_in = _is_torch(points)
         if torch_in and _cuda_device(self, points) is not None:    # resident: no copy, no synchronisation, torch's current stream
             dev = points.device
             di = self._dev_index(dev)
             pts, sc = points.detach().contiguous(), scalar32.detach().contiguous()
-            res = _resident_outputs("msm_long", dev, n, elements, terms if encoded else None, outs)
+            res = _resident_outputs(what, dev, n, elements, terms if encoded else None, outs)
             p = lambda t: ctypes.c_void_p(t.data_ptr())
             ptrs = [p(o) for o in res]
             if not elements:
                 ptrs.insert(1, ctypes.c_void_p(None))
-            resident = self._lib.d377_batch_long_msm_encoded_resident if encoded else self._lib.d377_batch_long_msm_resident
-            _native.check(resident(self._h, di, _torch_stream(dev), p(pts), p(sc), ctypes.c_size_t(m), ctypes.c_size_t(n), *ptrs))
+            resident = getattr(self._lib, resident_names[1 if encoded else 0])
+            _native.check(resident(self._h, di, _torch_stream(dev), p(pts), p(sc), ctypes.c_size_t(m), ctypes.c_size_t(n), *(list(extra) + ptrs)))
             return tuple(res) if len(res) > 1 else res[0]
         if torch_in:
             dev = points.device
@@ -627,7 +633,7 @@ class Context:
                 self._dev_index(dev)                             # (raises: there is no CPU path for tensors)
             if outs is not None:
                 for a, (spec, rows) in zip(outs, specs):
-                    _check(a, spec, rows, "msm_long output", dev)
+                    _check(a, spec, rows, what + " output", dev)
             pts = points.detach().cpu().numpy()
             pts = pts.view(np.uint64) if pts.dtype == np.int64 else pts
             sc = scalar32.detach().cpu().numpy()
@@ -640,7 +646,7 @@ class Context:
         ptrs = [p(o) for o in host]
         if not elements:
             ptrs.insert(1, ctypes.c_void_p(None))
-        _native.check(getattr(self._lib, name)(self._h, p(pts), p(sc), ctypes.c_size_t(m), ctypes.c_size_t(n), *ptrs))
+        _native.check(getattr(self._lib, name)(self._h, p(pts), p(sc), ctypes.c_size_t(m), ctypes.c_size_t(n), *(list(extra) + ptrs)))
         if torch_in:
             import torch
             res = [torch.from_numpy(h.view(np.int64) if h.dtype == np.uint64 else h).to(dev) for h in host]
@@ -650,6 +656,26 @@ class Context:
                 res = list(outs)
             return tuple(res) if len(res) > 1 else res[0]
         return tuple(host) if len(host) > 1 else host[0]
+
+    def msm_buckets(self, points, scalar32, m, outs=None, elements=False, window_bits=0):
+        """n independent multiscalar sums of m terms each, 1 <= m <= 2^20, by the bucket method
+        (d377_batch_bucket_msm[_encoded], include/decaf377_amd_bucket_sums.h): the sums of a pass share one run of msm()'s
+        sort / span / bucket pipeline under a composite bucket key.  Arguments, results and routing are msm_long's: points
+        [n * m, 16] u64 Elements or [n * m, 32] u8 Encodings, scalar32 [n * m, 32], term-major; tensors on a device of the
+        context take the resident form on torch's current stream (one eager call of a shape before capturing it in a graph).
+        window_bits: 0 = the library's width rule; 4 .. 16 forces the window width (a developer and test knob)."""
+        return self._sums_of_m("msm_buckets", ("d377_batch_bucket_msm", "d377_batch_bucket_msm_encoded"),
+                               ("d377_batch_bucket_msm_resident", "d377_batch_bucket_msm_encoded_resident"), points, scalar32, m, outs,
+                               elements, extra=(ctypes.c_int(int(window_bits)),))
+
+    def msm_buckets_plan(self, n, m, window_bits=0, dev=0):
+        """The plan of msm_buckets for n sums of m terms on device `dev` of the context (d377_bucket_msm_plan) ->
+        {"window_bits", "sums_per_pass", "passes", "workspace_bytes"}."""
+        c = ctypes.c_int(0)
+        spp, passes, ws = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _native.check(self._lib.d377_bucket_msm_plan(self._h, int(dev), ctypes.c_size_t(int(n)), ctypes.c_size_t(int(m)), int(window_bits),
+                                                     ctypes.byref(c), ctypes.byref(spp), ctypes.byref(passes), ctypes.byref(ws)))
+        return {"window_bits": c.value, "sums_per_pass": spp.value, "passes": passes.value, "workspace_bytes": ws.value}
 
     def msm_long_indexed(self, pool, point_index, scalar32, m, elements=False, check_indices=True, outs=None):
         """n sums of m terms that name their points in a shared pool (d377_batch_long_msm_indexed):

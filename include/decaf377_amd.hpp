@@ -563,6 +563,31 @@ class Engine {
                                                reinterpret_cast<const uint8_t*>(scalars), m, n, reinterpret_cast<uint8_t*>(enc_out),
                                                reinterpret_cast<uint64_t*>(elements_out), verdict));
   }
+  /// MANY sums of up to 2^20 terms each by the bucket method (d377_batch_bucket_msm, decaf377_amd_bucket_sums.h): the sums of a
+  /// pass share one run of vartime_multiscalar_mul's sort / span / bucket pipeline.  window_bits: 0 = the library's rule,
+  /// 4 .. 16 forces the window width (a developer and test knob).
+  std::vector<Element> vartime_multiscalar_mul_batch_buckets(size_t m, const std::vector<Fr>& scalars, const std::vector<Element>& points,
+                                                             std::vector<Encoding>* encodings = nullptr, int window_bits = 0) {
+    if (scalars.size() != points.size() || m == 0 || points.size() % m) throw std::invalid_argument("length mismatch");
+    std::vector<Element> out(points.size() / m);
+    std::vector<Encoding> enc(out.size());
+    check(d377_batch_bucket_msm(ctx_, u64(points), u8(scalars), m, out.size(), window_bits, u8m(enc), reinterpret_cast<uint64_t*>(out.data())));
+    if (encodings) *encodings = std::move(enc);
+    return out;
+  }
+  /// ... on DEVICE pointers of device `dev` of the Engine (records 16-byte aligned): enqueues on `stream` and returns.  One eager
+  /// call of a shape must come before it is captured into a graph (the MSM workspace cannot grow inside a capture).
+  void msm_buckets_resident(int dev, void* stream, const Element* points, const Fr* scalars, size_t m, size_t n, Encoding* enc_out,
+                            Element* elements_out = nullptr, int window_bits = 0) {
+    check(d377_batch_bucket_msm_resident(ctx_, dev, stream, reinterpret_cast<const uint64_t*>(points), reinterpret_cast<const uint8_t*>(scalars), m, n,
+                                         window_bits, reinterpret_cast<uint8_t*>(enc_out), reinterpret_cast<uint64_t*>(elements_out)));
+  }
+  void msm_buckets_resident(int dev, void* stream, const Encoding* points, const Fr* scalars, size_t m, size_t n, Encoding* enc_out,
+                            Element* elements_out, uint8_t* status, int window_bits = 0) {
+    check(d377_batch_bucket_msm_encoded_resident(ctx_, dev, stream, reinterpret_cast<const uint8_t*>(points), reinterpret_cast<const uint8_t*>(scalars),
+                                                 m, n, window_bits, reinterpret_cast<uint8_t*>(enc_out), reinterpret_cast<uint64_t*>(elements_out),
+                                                 status));
+  }
   /// CurveGroup::normalize_batch (src/ark_curve/element.rs:74-81): affine (x, y) as 4 Montgomery limbs each
   std::vector<std::array<uint64_t, 8>> normalize_batch(const std::vector<Element>& p) {
     std::vector<std::array<uint64_t, 8>> out(p.size());

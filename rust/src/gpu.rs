@@ -38,6 +38,8 @@ pub mod ffi;
 pub mod ffi_resident;                                             // rust/src/ffi_resident.rs, from include/decaf377_amd_resident.h
 #[path = "gpu/ffi_long_sums.rs"]
 pub mod ffi_long_sums;                                            // rust/src/ffi_long_sums.rs, from include/decaf377_amd_long_sums.h
+#[path = "gpu/ffi_bucket_sums.rs"]
+pub mod ffi_bucket_sums;                                          // rust/src/ffi_bucket_sums.rs, from include/decaf377_amd_bucket_sums.h
 
 /// Which backend's root `sqrt_ratio_zeta_batch` returns (the flags are the same).
 #[derive(Copy, Clone, Debug, PartialEq, Eq)]
@@ -550,6 +552,22 @@ impl Element {
         })?;
         Ok((out.chunks_exact(16).map(element_from_xyzt).collect(), enc, results(&st, |_| ())))
     }
+    /// MANY sums of up to 2^20 terms each by the bucket method (d377_batch_bucket_msm): the sums of a pass share one run of
+    /// `vartime_multiscalar_mul_gpu`'s sort / span / bucket pipeline.  The only call for several sums of more than 4096 terms.
+    pub fn vartime_multiscalar_mul_batch_buckets_gpu(ctx: &GpuContext, m: usize, scalars: &[Fr], points: &[Element])
+        -> Result<(Vec<Element>, Vec<Encoding>), GpuError> {
+        assert_eq!(scalars.len(), points.len());
+        assert!(m >= 1 && points.len() % m == 0);
+        let n = points.len() / m;
+        let xyzt = elements_to_xyzt(points);
+        let bytes = pack32(scalars, |k| k.to_bytes());
+        let mut enc = vec![Encoding([0u8; 32]); n];
+        let mut out = vec![0u64; 16 * n];
+        check(unsafe {
+            ffi_bucket_sums::d377_batch_bucket_msm(ctx.0, xyzt.as_ptr(), bytes.as_ptr(), m, n, 0, enc.as_mut_ptr() as *mut u8, out.as_mut_ptr())
+        })?;
+        Ok((out.chunks_exact(16).map(element_from_xyzt).collect(), enc))
+    }
     /// Long sums whose terms name their points: sum i = sum over j < m of scalars[i m + j] * pool[point_index[i m + j]]
     /// (d377_batch_long_msm_indexed).  -1 is an absent term; any other index outside the pool is refused before any launch.
     pub fn vartime_multiscalar_mul_batch_long_indexed_gpu(ctx: &GpuContext, m: usize, pool: &[Element], point_index: &[i32], scalars: &[Fr])
@@ -780,5 +798,18 @@ pub mod dev {
                                             xyzt_out: *mut u64, verdict: *mut u64) -> Result<(), GpuError> {
         check(ffi_long_sums::d377_batch_long_msm_indexed_resident(ctx.0, dev, stream, pool_xyzt, pool_count, point_index, scalar32, m, n,
                                                                   enc32_out, xyzt_out, verdict))
+    }
+
+    // Many sums by the bucket method on device buffers (ffi_bucket_sums.rs): `xyzt_out` may be null; window_bits 0 = the
+    // library's rule.  One eager call of a shape before it is captured into a graph (the MSM workspace cannot grow in a capture).
+    pub unsafe fn msm_buckets_resident(ctx: &GpuContext, dev: i32, stream: *mut c_void, xyzt: *const u64, scalar32: *const u8, m: usize,
+                                       n: usize, window_bits: i32, enc32_out: *mut u8, xyzt_out: *mut u64) -> Result<(), GpuError> {
+        check(ffi_bucket_sums::d377_batch_bucket_msm_resident(ctx.0, dev, stream, xyzt, scalar32, m, n, window_bits, enc32_out, xyzt_out))
+    }
+    pub unsafe fn msm_buckets_encoded_resident(ctx: &GpuContext, dev: i32, stream: *mut c_void, enc32: *const u8, scalar32: *const u8,
+                                               m: usize, n: usize, window_bits: i32, enc32_out: *mut u8, xyzt_out: *mut u64,
+                                               status: *mut u8) -> Result<(), GpuError> {
+        check(ffi_bucket_sums::d377_batch_bucket_msm_encoded_resident(ctx.0, dev, stream, enc32, scalar32, m, n, window_bits, enc32_out,
+                                                                      xyzt_out, status))
     }
 }
