@@ -36,12 +36,6 @@ def _torch_stream(dev):
     return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
-def _cuda_device(ctx, *arrays):
-    """The device of the first tensor among `arrays` that lives on a device of `ctx`, or None: which calls take the resident
-    forms.  Every other input -- numpy, CPU tensors, tensors on a GPU the context does not own -- keeps the host path."""
-    return next((a.device for a in arrays if _is_torch(a) and a.device.type == "cuda" and a.device.index in ctx.device_ids), None)
-
-
 def _rows(a):
     if a.ndim < 1:
         raise ValueError("expected a [n, k] array of packed records")
@@ -83,7 +77,14 @@ def _check(a, spec, n, what, device=None):
         raise ValueError("%s: expected %s elements, got %s" % (what, "uint8" if kind == "u8" else "uint64/int64", a.dtype))
 
 
-# ---- what the resident routes of Context and FixedBases share
+# ---- what the batched sums of Context and FixedBases share: every argument rule once, on numpy arrays for the host route
+# (dev None) and on tensors for the resident route (dev: the device of the context the call runs on)
+def _cuda_device(ctx, *arrays):
+    """The device of the first tensor among `arrays` that lives on a device of `ctx`, or None: which calls take the resident
+    forms.  Every other input -- numpy, CPU tensors, tensors on a GPU the context does not own -- keeps the host path."""
+    return next((a.device for a in arrays if _is_torch(a) and a.device.type == "cuda" and a.device.index in ctx.device_ids), None)
+
+
 def _on_device(dev, a):
     """`a` as a contiguous tensor on `dev` (a numpy array or a tensor that lives elsewhere is copied there)."""
     import torch
@@ -93,11 +94,74 @@ def _on_device(dev, a):
     return a.detach().to(dev).contiguous()
 
 
-def _resident_outputs(what, dev, n, elements, status_rows=None, outs=None):
-    """The outputs of a resident call on `dev`: enc [n, 32], xyzt [n, 16] with elements, status [status_rows] for
-    Encodings -- allocated there, or the caller's `outs` in that order, checked like inputs."""
+def _staged(dev, a):
+    """`a` where the route reads it: a contiguous numpy array (a CPU tensor shares its memory with it, any other tensor is
+    copied to the host), or a contiguous tensor on `dev`."""
+    if dev is not None:
+        return _on_device(dev, a)
+    return np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a)
+
+
+def _is_u8(a):
+    if _is_torch(a):
+        import torch
+        return a.dtype == torch.uint8
+    return a.dtype == np.uint8
+
+
+def _ptr(a):
+    """The void* argument for an array of either kind, which the caller keeps alive through the call; None is NULL."""
+    if a is None:
+        return None
+    return ctypes.c_void_p(a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr())
+
+
+def _index(dev, index, what, arg, rule="must be an [n, t] integer array"):
+    """`index` as a contiguous [n, t] int32 array of the route's kind.  Any integer type is accepted and converted; one that
+    holds a value outside 32 bits is refused (on the resident route one synchronising reduction, for wider types only)."""
+    if dev is None:
+        idx = np.asarray(index.detach().cpu().numpy() if _is_torch(index) else index)
+        integer, i32 = idx.dtype.kind in "iu", np.int32
+    else:
+        import torch
+        idx = index if _is_torch(index) else torch.from_numpy(np.ascontiguousarray(index))
+        integer, i32 = idx.dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64), torch.int32
+    if idx.ndim != 2 or not integer:
+        raise ValueError("%s: %s %s" % (what, arg, rule))
+    if dev is not None:
+        idx = idx.detach().to(dev)
+    if idx.dtype != i32:
+        if 0 not in idx.shape and (int(idx.min()) < -(1 << 31) or int(idx.max()) >= (1 << 31)):
+            raise ValueError("%s: %s does not fit 32 bits" % (what, arg))
+        idx = idx.astype(i32) if dev is None else idx.to(i32)
+    return np.ascontiguousarray(idx) if dev is None else idx.contiguous()
+
+
+def _records(dev, a, spec, n, t, mismatch, what):
+    """[n * t, k] or [n, t, k] records that go with an [n, t] index -> the staged [n * t, k] array, checked against `spec`;
+    `mismatch`: the caller's text for an [n, t, k] array whose first two dimensions are not the index's."""
+    a = _staged(dev, a)
+    if a.ndim == 3:
+        if tuple(a.shape[:2]) != (n, t):
+            raise ValueError(mismatch)
+        a = a.reshape((n * t,) + spec[0])
+    _check(a, spec, n * t, what)
+    return a
+
+
+def _out_specs(n, elements, status_rows=None):
+    """(row layout, rows) of the outputs of a sums call, in the C order: enc, xyzt with elements, status for Encodings."""
+    return [(ENC, n)] + ([(ELEM, n)] if elements else []) + ([(FLAG, status_rows)] if status_rows is not None else [])
+
+
+def _outputs(what, dev, n, elements, status_rows=None, outs=None):
+    """The outputs of a sums call: enc [n, 32], xyzt [n, 16] with elements, status [status_rows] for Encodings -- numpy arrays on
+    the host route; on the resident route tensors allocated on `dev`, or the caller's `outs` in that order, checked like inputs."""
+    if dev is None:
+        res = [np.zeros((n, 32), np.uint8)] + ([np.zeros((n, 16), np.uint64)] if elements else [])
+        return res + [np.zeros((status_rows,), np.uint8)] if status_rows is not None else res
     import torch
-    specs = [(ENC, n)] + ([(ELEM, n)] if elements else []) + ([(FLAG, status_rows)] if status_rows is not None else [])
+    specs = _out_specs(n, elements, status_rows)
     if outs is None:
         return [torch.empty((rows,) + tail, dtype=torch.uint8 if k == "u8" else torch.int64, device=dev) for (tail, k), rows in specs]
     if len(outs) != len(specs):
@@ -111,19 +175,31 @@ def _resident_outputs(what, dev, n, elements, status_rows=None, outs=None):
     return list(outs)
 
 
-def _resident_index(dev, index, what, arg):
-    """`index` as a contiguous [n, t] int32 tensor on `dev`; an int64 index outside 32 bits is the ValueError of the
-    host path (one synchronising reduction, for int64 tensors only)."""
-    import torch
-    idx = index if _is_torch(index) else torch.from_numpy(np.ascontiguousarray(index))
-    if idx.ndim != 2 or idx.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
-        raise ValueError("%s: %s must be an [n, t] integer array" % (what, arg))
-    idx = idx.detach().to(dev)
-    if idx.dtype != torch.int32:
-        if idx.numel() and (int(idx.min()) < -(1 << 31) or int(idx.max()) >= (1 << 31)):
-            raise ValueError("%s: %s does not fit 32 bits" % (what, arg))
-        idx = idx.to(torch.int32)
-    return idx.contiguous()
+def _out_ptrs(res, elements):
+    """The output pointers in the C order enc, xyzt, [status]: xyzt is NULL without elements."""
+    ptrs = [_ptr(a) for a in res]
+    if not elements:
+        ptrs.insert(1, None)
+    return ptrs
+
+
+def _results(res, dev, arrays, verdict=None, into=None):
+    """What a sums call returns: its outputs, the verdict tensor of an unchecked resident call appended; one array alone is
+    returned bare.  The host route's arrays go to the device of the first tensor among the caller's `arrays`, when there is
+    one (Element records as int64 there), and from there into the caller's own tensors `into`, when it gave some."""
+    if dev is None:
+        for given in arrays:
+            if _is_torch(given):
+                import torch
+                res = [torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(given.device) for a in res]
+                if into is not None:
+                    for o, r in zip(into, res):
+                        o.copy_(r)
+                    res = list(into)
+                break
+    if verdict is not None:
+        res = list(res) + [verdict]
+    return tuple(res) if len(res) > 1 else res[0]
 
 
 def _verdict_tensor(dev, n):
@@ -133,6 +209,13 @@ def _verdict_tensor(dev, n):
     if n == 0:
         verdict[1] = -1
     return verdict
+
+
+def _refused_index(symbol, arg, first, value, t, noun):
+    """The native library's text for the first refused index of an [n, t] array, restated for the resident routes: there the
+    library has made no refusal whose text could be read.  tests/test_resident_sums_gpu.py::
+    test_python_checks_the_indices_before_any_launch compares the two texts."""
+    return _native.error(-2, "%s: %s[%d] = %d (sum %d, term %d) is neither -1 nor a %s" % (symbol, arg, first, value, first // t, first % t, noun))
 
 
 class Context:
@@ -541,48 +624,9 @@ class Context:
         Encodings (an invalid Encoding is reported and left out of its sum); with elements=True the sums also come back as
         Element records, what the reference's function returns: (enc, xyzt [n, 16]) / (enc, xyzt, status), in d377_msm's
         order.  outs: the same tuple of preallocated arrays."""
-        m = int(m)
-        if points.ndim != 2 or int(points.shape[1]) not in (16, 32):
-            raise ValueError("msm_small: points must be [n * m, 16] Elements or [n * m, 32] Encodings")
-        encoded = int(points.shape[1]) == 32
-        terms = _rows(points)
-        if m < 1 or terms % m:
-            raise ValueError("msm_small: the number of points must be a multiple of m")
-        n = terms // m
-        _check(points, ENC if encoded else ELEM, terms, "msm_small points")
-        _check(scalar32, ENC, terms, "msm_small scalars", points.device if _is_torch(points) else None)
-        name = "d377_batch_msm_small_encoded" if encoded else "d377_batch_msm_small"
-        specs = [(ENC, n)] + ([(ELEM, n)] if elements else []) + ([(FLAG, terms)] if encoded else [])
-        null = ctypes.c_void_p(None)
-        if _is_torch(points):
-            import torch
-            dev = points.device
-            di = self._dev_index(dev)
-            pts, sc = points.contiguous(), scalar32.contiguous()
-            if outs is None:
-                outs = [torch.empty((rows,) + tail, dtype=torch.uint8 if k == "u8" else torch.int64, device=dev) for (tail, k), rows in specs]
-            if len(outs) != len(specs):
-                raise ValueError("msm_small: %d output arrays expected" % len(specs))
-            for a, (spec, rows) in zip(outs, specs):
-                _check(a, spec, rows, "msm_small output", dev)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            p = lambda t: ctypes.c_void_p(t.data_ptr())
-            ptrs = [p(o) for o in outs]
-            if not elements:
-                ptrs.insert(1, null)
-            _native.check(getattr(self._lib, name + "_dev")(self._h, di, stream, p(pts), p(sc), ctypes.c_size_t(m), ctypes.c_size_t(n), *ptrs))
-            return tuple(outs) if len(outs) > 1 else outs[0]
-        pts, sc = np.ascontiguousarray(points), np.ascontiguousarray(scalar32)
-        if outs is None:
-            outs = [np.zeros((rows,) + tail, np.uint8 if k == "u8" else np.uint64) for (tail, k), rows in specs]
-        if len(outs) != len(specs):
-            raise ValueError("msm_small: %d output arrays expected" % len(specs))
-        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        ptrs = [p(o) for o in outs]
-        if not elements:
-            ptrs.insert(1, null)
-        _native.check(getattr(self._lib, name)(self._h, p(pts), p(sc), ctypes.c_size_t(m), ctypes.c_size_t(n), *ptrs))
-        return tuple(outs) if len(outs) > 1 else outs[0]
+        return self._sums_of_m("msm_small", ("d377_batch_msm_small", "d377_batch_msm_small_encoded"),
+                               ("d377_batch_msm_small_dev", "d377_batch_msm_small_encoded_dev"), points, scalar32, m, outs, elements,
+                               stage_foreign=False)
 
     def msm_long(self, points, scalar32, m, outs=None, elements=False):
         """n independent multiscalar sums of m terms each, 1 <= m <= 4096 (d377_batch_msm_long[_encoded]): msm_small's sums
@@ -597,9 +641,19 @@ class Context:
         return self._sums_of_m("msm_long", ("d377_batch_msm_long", "d377_batch_msm_long_encoded"),
                                ("d377_batch_long_msm_resident", "d377_batch_long_msm_encoded_resident"), points, scalar32, m, outs, elements)
 
-    def _sums_of_m(self, what, host_names, resident_names, points, scalar32, m, outs, elements, extra=()):
-        """What msm_long and msm_buckets share: n sums of m terms, host or resident by where the points live; `extra`: the
-        call's own arguments between n and the outputs."""
+    def _launch(self, dev, host_symbol, device_symbol, *args):
+        """One native call of a sums family: `host_symbol`(ctx, *args) on the host route (dev None), else
+        `device_symbol`(ctx, device index, torch's current stream on dev, *args)."""
+        if dev is None:
+            _native.check(getattr(self._lib, host_symbol)(self._h, *args))
+        else:
+            _native.check(getattr(self._lib, device_symbol)(self._h, self._dev_index(dev), _torch_stream(dev), *args))
+
+    def _sums_of_m(self, what, host_names, device_names, points, scalar32, m, outs, elements, extra=(), stage_foreign=True):
+        """What msm_small, msm_long and msm_buckets share: n sums of m terms, on the host or on the device by where the points
+        live; `extra`: the call's own arguments between n and the outputs.  stage_foreign: a tensor on a GPU the context does
+        not own is staged through host memory (msm_long, msm_buckets); without it every tensor takes the device call, which
+        refuses such a tensor (msm_small)."""
         m = int(m)
         if points.ndim != 2 or int(points.shape[1]) not in (16, 32):
             raise ValueError("%s: " % what + "points must be [n * m, 16] Elements or [n * m, 32] Encodings")
@@ -608,54 +662,30 @@ class Context:
         if m < 1 or terms % m:
             raise ValueError("%s: " % what + "the number of points must be a multiple of m")
         n = terms // m
+        tdev = points.device if _is_torch(points) else None
         _check(points, ENC if encoded else ELEM, terms, what + " points")
-        _check(scalar32, ENC, terms, what + " scalars", points.device if _is_torch(points) else None)
-        name = host_names[1 if encoded else 0]
-        specs = [(ENC, n)] + ([(ELEM, n)] if elements else []) + ([(FLAG, terms)] if encoded else [])
+        _check(scalar32, ENC, terms, what + " scalars", tdev)
+        status_rows = terms if encoded else None
+        specs = _out_specs(n, elements, status_rows) if outs is not None else None
         if outs is not None and len(outs) != len(specs):
             raise ValueError("%s: " % what + "%d output arrays expected" % len(specs))
-        torch_in = _is_torch(points)
-        if torch_in and _cuda_device(self, points) is not None:    # resident: no copy, no synchronisation, torch's current stream
-            dev = points.device
-            di = self._dev_index(dev)
+        dev = tdev if tdev is not None and (not stage_foreign or _cuda_device(self, points) is not None) else None
+        if dev is not None:                                      # no copy, no synchronisation, torch's current stream
+            self._dev_index(dev)                                 # (raises for a tensor that is on no device of the context)
             pts, sc = points.detach().contiguous(), scalar32.detach().contiguous()
-            res = _resident_outputs(what, dev, n, elements, terms if encoded else None, outs)
-            p = lambda t: ctypes.c_void_p(t.data_ptr())
-            ptrs = [p(o) for o in res]
-            if not elements:
-                ptrs.insert(1, ctypes.c_void_p(None))
-            resident = getattr(self._lib, resident_names[1 if encoded else 0])
-            _native.check(resident(self._h, di, _torch_stream(dev), p(pts), p(sc), ctypes.c_size_t(m), ctypes.c_size_t(n), *(list(extra) + ptrs)))
-            return tuple(res) if len(res) > 1 else res[0]
-        if torch_in:
-            dev = points.device
-            if dev.type != "cuda":
-                self._dev_index(dev)                             # (raises: there is no CPU path for tensors)
-            if outs is not None:
-                for a, (spec, rows) in zip(outs, specs):
-                    _check(a, spec, rows, what + " output", dev)
-            pts = points.detach().cpu().numpy()
-            pts = pts.view(np.uint64) if pts.dtype == np.int64 else pts
-            sc = scalar32.detach().cpu().numpy()
-            host = [np.zeros((rows,) + tail, np.uint8 if k == "u8" else np.uint64) for (tail, k), rows in specs]
+            res = _outputs(what, dev, n, elements, status_rows, outs)
         else:
-            pts, sc = points, scalar32
-            host = outs if outs is not None else [np.zeros((rows,) + tail, np.uint8 if k == "u8" else np.uint64) for (tail, k), rows in specs]
-        pts, sc = np.ascontiguousarray(pts), np.ascontiguousarray(sc)
-        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        ptrs = [p(o) for o in host]
-        if not elements:
-            ptrs.insert(1, ctypes.c_void_p(None))
-        _native.check(getattr(self._lib, name)(self._h, p(pts), p(sc), ctypes.c_size_t(m), ctypes.c_size_t(n), *(list(extra) + ptrs)))
-        if torch_in:
-            import torch
-            res = [torch.from_numpy(h.view(np.int64) if h.dtype == np.uint64 else h).to(dev) for h in host]
-            if outs is not None:
-                for o, r in zip(outs, res):
-                    o.copy_(r)
-                res = list(outs)
-            return tuple(res) if len(res) > 1 else res[0]
-        return tuple(host) if len(host) > 1 else host[0]
+            if tdev is not None:
+                if tdev.type != "cuda":
+                    self._dev_index(tdev)                        # (raises: there is no CPU path for tensors)
+                if outs is not None:
+                    for a, (spec, rows) in zip(outs, specs):
+                        _check(a, spec, rows, what + " output", tdev)
+            pts, sc = _staged(None, points), _staged(None, scalar32)
+            res = outs if outs is not None and tdev is None else _outputs(what, None, n, elements, status_rows)
+        self._launch(dev, host_names[encoded], device_names[encoded], _ptr(pts), _ptr(sc), ctypes.c_size_t(m), ctypes.c_size_t(n),
+                     *extra, *_out_ptrs(res, elements))
+        return _results(res, dev, (points,), into=outs)
 
     def msm_buckets(self, points, scalar32, m, outs=None, elements=False, window_bits=0):
         """n independent multiscalar sums of m terms each, 1 <= m <= 2^20, by the bucket method
@@ -704,69 +734,29 @@ class Context:
         pool_count = _rows(pool)
         _check(pool, ELEM, pool_count, what + " pool")
         dev = _cuda_device(self, pool, point_index, scalar32)
-        if dev is not None:
-            di = self._dev_index(dev)
-            idx = _resident_index(dev, point_index, what, "point_index")
-            n = int(idx.shape[0])
-            if int(idx.shape[1]) != m:
-                raise ValueError(what + ": point_index must be [n, m]")
-            pl, sc = _on_device(dev, pool), _on_device(dev, scalar32)
-            if sc.ndim == 3:
-                if tuple(sc.shape[:2]) != (n, m):
-                    raise ValueError(what + ": scalars [n, m, 32] must match point_index [n, m]")
-                sc = sc.reshape(n * m, 32)
-            _check(sc, ENC, n * m, what + " scalars")
-            verdict = None
-            if check_indices:
-                flat = idx.reshape(-1)
-                bad = ((flat != -1) & ((flat < 0) | (flat >= pool_count))).nonzero()
-                if bad.numel():                                  # (the one synchronisation) the host form's text, restated
-                    first = int(bad[0])
-                    raise _native.error(-2, "d377_batch_long_msm_indexed: point_index[%d] = %d (sum %d, term %d) is neither -1 nor a "
-                                        "record 0 .. %d of the pool" % (first, int(flat[first]), first // m, first % m, pool_count - 1))
-            else:
-                verdict = _verdict_tensor(dev, n)
-            res = _resident_outputs(what, dev, n, elements, outs=outs)
-            p = lambda a: ctypes.c_void_p(a.data_ptr())
-            _native.check(self._lib.d377_batch_long_msm_indexed_resident(
-                self._h, di, _torch_stream(dev), p(pl), ctypes.c_size_t(pool_count), p(idx), p(sc), ctypes.c_size_t(m), ctypes.c_size_t(n),
-                p(res[0]), p(res[1]) if elements else None, p(verdict) if verdict is not None else None))
-            if verdict is not None:
-                res.append(verdict)
-            return tuple(res) if len(res) > 1 else res[0]
-        if outs is not None:
+        if dev is None and outs is not None:
             raise ValueError(what + ": outs goes with tensors on a device of the context")
-        tdev = next((a.device for a in (pool, point_index, scalar32) if _is_torch(a)), None)
-        host = lambda a: a.detach().cpu().numpy() if _is_torch(a) else a
-        idx = np.asarray(host(point_index))
-        if idx.ndim != 2 or idx.dtype.kind not in "iu":
-            raise ValueError(what + ": point_index must be an [n, m] integer array")
+        idx = _index(dev, point_index, what, "point_index", "must be an [n, m] integer array")
         n = int(idx.shape[0])
         if int(idx.shape[1]) != m:
             raise ValueError(what + ": point_index must be [n, m]")
-        if idx.dtype != np.int32:
-            if idx.size and (int(idx.min()) < -(1 << 31) or int(idx.max()) >= (1 << 31)):
-                raise ValueError(what + ": point_index does not fit 32 bits")
-            idx = idx.astype(np.int32)
-        idx = np.ascontiguousarray(idx)
-        pl = np.ascontiguousarray(host(pool))
-        sc = np.ascontiguousarray(host(scalar32))
-        if sc.ndim == 3:
-            if sc.shape[:2] != (n, m):
-                raise ValueError(what + ": scalars [n, m, 32] must match point_index [n, m]")
-            sc = sc.reshape(n * m, 32)
-        _check(sc, ENC, n * m, what + " scalars")
-        enc = np.empty((n, 32), np.uint8)
-        xyzt = np.empty((n, 16), np.uint64) if elements else None
-        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        _native.check(self._lib.d377_batch_long_msm_indexed(self._h, p(pl), ctypes.c_size_t(pool_count), p(idx), p(sc), ctypes.c_size_t(m),
-                                                            ctypes.c_size_t(n), p(enc), p(xyzt) if elements else None))
-        if tdev is not None:
-            import torch
-            enc = torch.from_numpy(enc).to(tdev)
-            if elements:
-                xyzt = torch.from_numpy(xyzt.view(np.int64)).to(tdev)
-        return (enc, xyzt) if elements else enc
+        pl = _staged(dev, pool)
+        sc = _records(dev, scalar32, ENC, n, m, what + ": scalars [n, m, 32] must match point_index [n, m]", what + " scalars")
+        verdict = None
+        if dev is not None and check_indices:
+            flat = idx.reshape(-1)
+            bad = ((flat != -1) & ((flat < 0) | (flat >= pool_count))).nonzero()
+            if bad.numel():                                      # (the one synchronisation)
+                first = int(bad[0])
+                raise _refused_index("d377_batch_long_msm_indexed", "point_index", first, int(flat[first]), m,
+                                     "record 0 .. %d of the pool" % (pool_count - 1))
+        elif dev is not None:
+            verdict = _verdict_tensor(dev, n)
+        res = _outputs(what, dev, n, elements, outs=outs)
+        self._launch(dev, "d377_batch_long_msm_indexed", "d377_batch_long_msm_indexed_resident", _ptr(pl), ctypes.c_size_t(pool_count),
+                     _ptr(idx), _ptr(sc), ctypes.c_size_t(m), ctypes.c_size_t(n), *_out_ptrs(res, elements),
+                     *(() if dev is None else (_ptr(verdict),)))
+        return _results(res, dev, (pool, point_index, scalar32), verdict)
 
     def msm(self, points, scalar32, encoded=None):
         """Element::vartime_multiscalar_mul (src/ark_curve/element/projective.rs:99-117).
@@ -895,69 +885,36 @@ class FixedBases:
         _native.check(self._lib.d377_fixed_long_msm_plan(self.ctx._h, self._live(), ctypes.c_size_t(n), int(dev), ctypes.byref(g), ctypes.byref(b)))
         return int(g.value), int(b.value)
 
-    def _on_device(self, dev, a):
-        return _on_device(dev, a)
-
-    def _outputs(self, what, dev, n, elements, status_rows=None, outs=None):
-        return _resident_outputs(what, dev, n, elements, status_rows, outs)
-
     def _dense(self, symbol, what, scalar32, elements):
         h = self._live()
         dev = _cuda_device(self.ctx, scalar32)
-        if dev is not None:                                   # resident: no copy, no synchronisation, torch's current stream
-            di = self.ctx._dev_index(dev)
-            sc = scalar32.detach().contiguous()
-            terms = _rows(sc)
-            if terms % self.m:
-                raise ValueError("%s: the number of scalars must be a multiple of m = %d" % (what, self.m))
-            n = terms // self.m
-            _check(sc, ENC, terms, what + " scalars")
-            outs = self._outputs(what, dev, n, elements)
-            p = lambda t: ctypes.c_void_p(t.data_ptr())
-            _native.check(getattr(self._lib, symbol + "_resident")(self.ctx._h, di, _torch_stream(dev), h, p(sc), ctypes.c_size_t(n),
-                                                                   p(outs[0]), p(outs[1]) if elements else None))
-            return tuple(outs) if elements else outs[0]
-        tdev = scalar32.device if _is_torch(scalar32) else None
-        sc = np.ascontiguousarray(scalar32.detach().cpu().numpy() if tdev is not None else scalar32)
+        sc = _staged(dev, scalar32)
         terms = _rows(sc)
         if terms % self.m:
             raise ValueError("%s: the number of scalars must be a multiple of m = %d" % (what, self.m))
         n = terms // self.m
         _check(sc, ENC, terms, what + " scalars")
-        enc = np.empty((n, 32), np.uint8)
-        xyzt = np.empty((n, 16), np.uint64) if elements else None
-        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        _native.check(getattr(self._lib, symbol)(self.ctx._h, h, p(sc), ctypes.c_size_t(n), p(enc), p(xyzt) if elements else None))
-        if tdev is not None:
-            import torch
-            enc = torch.from_numpy(enc).to(tdev)
-            if elements:
-                xyzt = torch.from_numpy(xyzt.view(np.int64)).to(tdev)
-        return (enc, xyzt) if elements else enc
+        res = _outputs(what, dev, n, elements)
+        self.ctx._launch(dev, symbol, symbol + "_resident", h, _ptr(sc), ctypes.c_size_t(n), *_out_ptrs(res, elements))
+        return _results(res, dev, (scalar32,))
 
-    def _resident_index(self, dev, base_index, what):
-        return _resident_index(dev, base_index, what, "base_index")
-
-    @staticmethod
-    def _verdict_tensor(dev, n):
-        return _verdict_tensor(dev, n)
-
-    def _verdict(self, dev, di, idx, symbol):
-        """check_indices=True: d377_check_base_index_resident, then the one synchronisation -- the 16-byte record is read, and on
-        a refused index NativeError with the host form's text is raised before any sum is launched."""
+    def _verdict(self, dev, idx, check_indices, symbol):
+        """The index verdict of a resident call (None on the host route, where the library refuses by itself).
+        check_indices=True: d377_check_base_index_resident, then the one synchronisation -- the 16-byte record is read, and on
+        a refused index NativeError with the host form's text is raised before any sum is launched; returns None.
+        check_indices=False: the tensor the call writes its verdict to."""
+        if dev is None:
+            return None
+        if not check_indices:
+            return _verdict_tensor(dev, int(idx.shape[0]))
         import torch
         verdict = torch.empty((2,), dtype=torch.int64, device=dev)
-        _native.check(self._lib.d377_check_base_index_resident(self.ctx._h, di, _torch_stream(dev), self._live(), ctypes.c_void_p(idx.data_ptr()),
-                                                               ctypes.c_size_t(idx.numel()), ctypes.c_void_p(verdict.data_ptr())))
+        self.ctx._launch(dev, None, "d377_check_base_index_resident", self._live(), _ptr(idx), ctypes.c_size_t(idx.numel()), _ptr(verdict))
         count, first = (int(x) & ((1 << 64) - 1) for x in verdict.cpu().tolist())
         if count:
-            t = int(idx.shape[1])
-            b = int(idx.reshape(-1)[first].item())
-            # the host form's text (fixed_bases.hip, batch_msm_mixed.hip), restated: the library has made no refusal whose text
-            # could be read.  tests/test_resident_sums_gpu.py::test_python_checks_the_indices_before_any_launch compares the two
-            # and is the only guard against their drifting apart.
-            raise _native.error(-2, "%s: base_index[%d] = %d (sum %d, term %d) is neither -1 nor a base 0 .. %d of this registration"
-                                % (symbol, first, b, first // t, first % t, self.m - 1))
+            raise _refused_index(symbol, "base_index", first, int(idx.reshape(-1)[first].item()), int(idx.shape[1]),
+                                 "base 0 .. %d of this registration" % (self.m - 1))
+        return None
 
     def msm_indexed(self, base_index, scalar32, elements=False, check_indices=True, outs=None):
         """n sums of t terms that name their bases (d377_batch_fixed_msm_indexed):
@@ -979,61 +936,20 @@ class FixedBases:
         and msm_long's: preallocated contiguous tensors on that device in the order of the result, without the verdict, for
         callers that keep their buffers (a captured graph, a pipeline); the host route allocates its own arrays and
         refuses outs with ValueError."""
+        what = "FixedBases.msm_indexed"
         h = self._live()
         dev = _cuda_device(self.ctx, scalar32, base_index)
-        if dev is not None:
-            what = "FixedBases.msm_indexed"
-            di = self.ctx._dev_index(dev)
-            idx = self._resident_index(dev, base_index, what)
-            n, t = (int(x) for x in idx.shape)
-            sc = self._on_device(dev, scalar32)
-            if sc.ndim == 3:
-                if tuple(sc.shape[:2]) != (n, t):
-                    raise ValueError(what + ": scalars [n, t, 32] must match base_index [n, t]")
-                sc = sc.reshape(n * t, 32)
-            _check(sc, ENC, n * t, what + " scalars")
-            verdict = None
-            if check_indices:
-                self._verdict(dev, di, idx, "d377_batch_fixed_msm_indexed")
-            else:
-                verdict = self._verdict_tensor(dev, n)
-            outs = self._outputs(what, dev, n, elements, outs=outs)
-            p = lambda a: ctypes.c_void_p(a.data_ptr())
-            _native.check(self._lib.d377_batch_fixed_msm_indexed_resident(
-                self.ctx._h, di, _torch_stream(dev), h, p(idx), p(sc), ctypes.c_size_t(t), ctypes.c_size_t(n), p(outs[0]),
-                p(outs[1]) if elements else None, p(verdict) if verdict is not None else None))
-            if verdict is not None:
-                outs.append(verdict)
-            return tuple(outs) if len(outs) > 1 else outs[0]
-        if outs is not None:
-            raise ValueError("FixedBases.msm_indexed: outs goes with tensors on a device of the context")
-        tdev = scalar32.device if _is_torch(scalar32) else (base_index.device if _is_torch(base_index) else None)
-        idx = np.asarray(base_index.detach().cpu().numpy() if _is_torch(base_index) else base_index)
-        if idx.ndim != 2 or idx.dtype.kind not in "iu":
-            raise ValueError("FixedBases.msm_indexed: base_index must be an [n, t] integer array")
-        n, t = idx.shape
-        if idx.dtype != np.int32:
-            if idx.size and (int(idx.min()) < -(1 << 31) or int(idx.max()) >= (1 << 31)):
-                raise ValueError("FixedBases.msm_indexed: base_index does not fit 32 bits")
-            idx = idx.astype(np.int32)
-        idx = np.ascontiguousarray(idx)
-        sc = np.ascontiguousarray(scalar32.detach().cpu().numpy() if _is_torch(scalar32) else scalar32)
-        if sc.ndim == 3:
-            if sc.shape[:2] != (n, t):
-                raise ValueError("FixedBases.msm_indexed: scalars [n, t, 32] must match base_index [n, t]")
-            sc = sc.reshape(n * t, 32)
-        _check(sc, ENC, n * t, "FixedBases.msm_indexed scalars")
-        enc = np.empty((n, 32), np.uint8)
-        xyzt = np.empty((n, 16), np.uint64) if elements else None
-        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        _native.check(self._lib.d377_batch_fixed_msm_indexed(self.ctx._h, h, p(idx), p(sc), ctypes.c_size_t(t), ctypes.c_size_t(n),
-                                                             p(enc), p(xyzt) if elements else None))
-        if tdev is not None:
-            import torch
-            enc = torch.from_numpy(enc).to(tdev)
-            if elements:
-                xyzt = torch.from_numpy(xyzt.view(np.int64)).to(tdev)
-        return (enc, xyzt) if elements else enc
+        if dev is None and outs is not None:
+            raise ValueError(what + ": outs goes with tensors on a device of the context")
+        idx = _index(dev, base_index, what, "base_index")
+        n, t = (int(x) for x in idx.shape)
+        sc = _records(dev, scalar32, ENC, n, t, what + ": scalars [n, t, 32] must match base_index [n, t]", what + " scalars")
+        symbol = "d377_batch_fixed_msm_indexed"
+        verdict = self._verdict(dev, idx, check_indices, symbol)
+        res = _outputs(what, dev, n, elements, outs=outs)
+        self.ctx._launch(dev, symbol, symbol + "_resident", h, _ptr(idx), _ptr(sc), ctypes.c_size_t(t), ctypes.c_size_t(n),
+                         *_out_ptrs(res, elements), *(() if dev is None else (_ptr(verdict),)))
+        return _results(res, dev, (scalar32, base_index), verdict)
 
     def msm_mixed(self, base_index, fixed_scalar32, points, var_scalar32, elements=False, check_indices=True, outs=None):
         """n mixed sums, registered bases plus variable points (d377_batch_msm_mixed[_encoded]):
@@ -1054,116 +970,33 @@ class FixedBases:
         (this route only) are preallocated tensors on that device in the order of the result, without the verdict."""
         what = "FixedBases.msm_mixed"
         h = self._live()
-        dev = _cuda_device(self.ctx, points, var_scalar32, fixed_scalar32, base_index)
-        if dev is not None:
-            return self._mixed_resident(dev, h, base_index, fixed_scalar32, points, var_scalar32, elements, check_indices, outs)
-        if outs is not None:
+        args = (points, var_scalar32, fixed_scalar32, base_index)
+        dev = _cuda_device(self.ctx, *args)
+        if dev is None and outs is not None:
             raise ValueError(what + ": outs goes with tensors on a device of the context")
-        tdev = next((a.device for a in (points, var_scalar32, fixed_scalar32, base_index) if _is_torch(a)), None)
-        host = lambda a: np.asarray(a.detach().cpu().numpy() if _is_torch(a) else a)
-        idx = host(base_index)
-        if idx.ndim != 2 or idx.dtype.kind not in "iu":
-            raise ValueError(what + ": base_index must be an [n, t] integer array")
-        n, t = idx.shape
-        if idx.dtype != np.int32:
-            if idx.size and (int(idx.min()) < -(1 << 31) or int(idx.max()) >= (1 << 31)):
-                raise ValueError(what + ": base_index does not fit 32 bits")
-            idx = idx.astype(np.int32)
-        idx = np.ascontiguousarray(idx)
-        fs = np.ascontiguousarray(host(fixed_scalar32))
-        if fs.ndim == 3:
-            if fs.shape[:2] != (n, t):
-                raise ValueError(what + ": fixed scalars [n, t, 32] must match base_index [n, t]")
-            fs = fs.reshape(n * t, 32)
-        _check(fs, ENC, n * t, what + " fixed scalars")
-        pts = np.ascontiguousarray(host(points))
-        if pts.ndim == 3:
-            if pts.shape[0] != n:
-                raise ValueError(what + ": points [n, v, .] must have one row per sum")
-            pts = pts.reshape(pts.shape[0] * pts.shape[1], pts.shape[2])
-        encoded = pts.dtype == np.uint8
-        terms = _rows(pts)
-        if n == 0 or terms % n:
-            if terms or n:
-                raise ValueError(what + ": the number of points must be a multiple of the number of sums")
-        v = terms // n if n else 1
-        _check(pts, ENC if encoded else ELEM, n * v, what + " points")
-        vs = np.ascontiguousarray(host(var_scalar32))
-        if vs.ndim == 3:
-            if vs.shape[:2] != (n, v):
-                raise ValueError(what + ": variable scalars [n, v, 32] must match the points [n, v, .]")
-            vs = vs.reshape(n * v, 32)
-        _check(vs, ENC, n * v, what + " variable scalars")
-        enc = np.empty((n, 32), np.uint8)
-        xyzt = np.empty((n, 16), np.uint64) if elements else None
-        status = np.zeros((n * v,), np.uint8) if encoded else None
-        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        if encoded:
-            _native.check(self._lib.d377_batch_msm_mixed_encoded(self.ctx._h, h, p(idx), p(fs), ctypes.c_size_t(t), p(pts), p(vs),
-                                                                 ctypes.c_size_t(v), ctypes.c_size_t(n), p(enc),
-                                                                 p(xyzt) if elements else None, p(status)))
-        else:
-            _native.check(self._lib.d377_batch_msm_mixed(self.ctx._h, h, p(idx), p(fs), ctypes.c_size_t(t), p(pts), p(vs),
-                                                         ctypes.c_size_t(v), ctypes.c_size_t(n), p(enc), p(xyzt) if elements else None))
-        if tdev is not None:
-            import torch
-            enc = torch.from_numpy(enc).to(tdev)
-            if elements:
-                xyzt = torch.from_numpy(xyzt.view(np.int64)).to(tdev)
-            if encoded:
-                status = torch.from_numpy(status).to(tdev)
-        out = (enc, xyzt) if elements else (enc,)
-        if encoded:
-            out = out + (status,)
-        return out if len(out) > 1 else out[0]
-
-    def _mixed_resident(self, dev, h, base_index, fixed_scalar32, points, var_scalar32, elements, check_indices, outs):
-        """msm_mixed on device buffers: the host path's shape rules on tensors, then the resident call."""
-        import torch
-        what = "FixedBases.msm_mixed"
-        di = self.ctx._dev_index(dev)
-        idx = self._resident_index(dev, base_index, what)
+        idx = _index(dev, base_index, what, "base_index")
         n, t = (int(x) for x in idx.shape)
-        fs = self._on_device(dev, fixed_scalar32)
-        if fs.ndim == 3:
-            if tuple(fs.shape[:2]) != (n, t):
-                raise ValueError(what + ": fixed scalars [n, t, 32] must match base_index [n, t]")
-            fs = fs.reshape(n * t, 32)
-        _check(fs, ENC, n * t, what + " fixed scalars")
-        pts = self._on_device(dev, points)
+        fs = _records(dev, fixed_scalar32, ENC, n, t, what + ": fixed scalars [n, t, 32] must match base_index [n, t]", what + " fixed scalars")
+        pts = _staged(dev, points)
         if pts.ndim == 3:
             if int(pts.shape[0]) != n:
                 raise ValueError(what + ": points [n, v, .] must have one row per sum")
             pts = pts.reshape(pts.shape[0] * pts.shape[1], pts.shape[2])
-        encoded = pts.dtype == torch.uint8
+        encoded = _is_u8(pts)
         terms = _rows(pts)
         if n == 0 or terms % n:
             if terms or n:
                 raise ValueError(what + ": the number of points must be a multiple of the number of sums")
         v = terms // n if n else 1
         _check(pts, ENC if encoded else ELEM, n * v, what + " points")
-        vs = self._on_device(dev, var_scalar32)
-        if vs.ndim == 3:
-            if tuple(vs.shape[:2]) != (n, v):
-                raise ValueError(what + ": variable scalars [n, v, 32] must match the points [n, v, .]")
-            vs = vs.reshape(n * v, 32)
-        _check(vs, ENC, n * v, what + " variable scalars")
+        vs = _records(dev, var_scalar32, ENC, n, v, what + ": variable scalars [n, v, 32] must match the points [n, v, .]",
+                      what + " variable scalars")
         symbol = "d377_batch_msm_mixed_encoded" if encoded else "d377_batch_msm_mixed"
-        verdict = None
-        if check_indices:
-            self._verdict(dev, di, idx, symbol)
-        else:
-            verdict = self._verdict_tensor(dev, n)
-        outs = self._outputs(what, dev, n, elements, n * v if encoded else None, outs)
-        p = lambda a: ctypes.c_void_p(a.data_ptr()) if a is not None else None
-        args = [self.ctx._h, di, _torch_stream(dev), h, p(idx), p(fs), ctypes.c_size_t(t), p(pts), p(vs), ctypes.c_size_t(v),
-                ctypes.c_size_t(n), p(outs[0]), p(outs[1]) if elements else None]
-        if encoded:
-            args.append(p(outs[-1]))
-        _native.check(getattr(self._lib, symbol + "_resident")(*args, p(verdict)))
-        if verdict is not None:
-            outs.append(verdict)
-        return tuple(outs) if len(outs) > 1 else outs[0]
+        verdict = self._verdict(dev, idx, check_indices, symbol)
+        res = _outputs(what, dev, n, elements, n * v if encoded else None, outs)
+        self.ctx._launch(dev, symbol, symbol + "_resident", h, _ptr(idx), _ptr(fs), ctypes.c_size_t(t), _ptr(pts), _ptr(vs),
+                         ctypes.c_size_t(v), ctypes.c_size_t(n), *_out_ptrs(res, elements), *(() if dev is None else (_ptr(verdict),)))
+        return _results(res, dev, args, verdict)
 
     def vartime_multiscalar_mul(self, scalars):
         """The sums' Encodings for an Fr batch (or [n * m, 32] array) of n x m scalars, term-major within a sum."""

@@ -5,12 +5,9 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-R = 2111115437357092606062206234695386632838870926408408195193685246394721360383
+from _sums_support import R, scalar_bytes as _scalar_bytes
+
 THREADS = 16
-
-
-def _scalar_bytes(v):
-    return np.frombuffer(int(v).to_bytes(32, "little"), np.uint8)
 
 
 def plan(m):

@@ -5,6 +5,7 @@ import numpy as np
 
 import _digit_cases as dc
 from _batch_msm_long_cases import oracle_fold  # noqa: F401  (re-exported)
+from _sums_support import scalar_bytes as _scalar_bytes
 
 R = dc.R
 MAX_TERMS = 1 << 20
@@ -53,10 +54,6 @@ def cover_scalars(c):
         chosen.append(h)
         want -= got
     return chosen
-
-
-def _scalar_bytes(v):
-    return np.frombuffer(int(v).to_bytes(32, "little"), np.uint8)
 
 
 def make_case(oracle, rng, n, m, c, encoded=False, projective=False):

@@ -1,16 +1,14 @@
 """What tests/test_fixed_msm_long_host.py and tests/test_fixed_msm_long_gpu.py share: the cut of
 decaf377_amd/csrc/fixed_msm_long_plan.hpp restated in Python, bases and scalars with the degenerate ones at the first position of
 a segment (the record the walk lifts with ge_from_cached_affine), and the oracle's sums two ways -- scalar multiplications and
-additions, and the byte-table fold of tests/test_fixed_bases_gpu.py (restated) for batches too large for the first."""
-from concurrent.futures import ThreadPoolExecutor
-
+additions, and the byte-table fold of tests/_sums_support.py for batches too large for the first."""
 import numpy as np
 
-R = 2111115437357092606062206234695386632838870926408408195193685246394721360383
+from _sums_support import R, scalar_bytes
+
 SPECIAL = [0, 1, R - 1, R, (1 << 256) - 1]
 KINDS = ["identity", "generator", "scaled", "torsion"]
 FOLD = 16
-THREADS = 16
 
 
 def plan(m, n, L, seg_min=1):
@@ -33,10 +31,6 @@ def levels(g):
         g = -(-g // FOLD)
         n += 1
     return n
-
-
-def scalar_bytes(v):
-    return np.frombuffer(int(v).to_bytes(32, "little"), np.uint8)
 
 
 def make_bases(oracle, rng, m, b):
@@ -80,40 +74,3 @@ def oracle_fold(oracle, bases, k, n, m):
     for j in range(1, m):
         acc = oracle.add_xyzt(acc, np.ascontiguousarray(terms[:, j]))
     return oracle.compress(acc), acc
-
-
-class Fold:
-    """The oracle's sums over fixed bases the way a comb does them, with the oracle's own group law: k B = sum_w (byte w of
-    k mod r) 256^w B, the 32 x 256 multiples of each base made once by oracle additions and doublings and every term folded
-    by oracle additions on THREADS threads (tests/test_fixed_bases_gpu.py's Fold, restated)."""
-
-    def __init__(self, oracle, bases):
-        self.o = oracle
-        self.m = bases.shape[0]
-        ident = oracle.identity_xyzt()
-        tabs = np.zeros((self.m, 32, 256, 16), np.uint64)
-        p = np.ascontiguousarray(bases, dtype=np.uint64)
-        for w in range(32):
-            acc = np.tile(ident, (self.m, 1))
-            for b in range(256):
-                tabs[:, w, b] = acc
-                acc = oracle.add_xyzt(acc, p)
-            for _ in range(8):
-                p = oracle.double_xyzt(p)
-        self.tabs = tabs
-
-    def _part(self, kb, lo, hi):
-        acc = np.tile(self.o.identity_xyzt(), (hi - lo, 1))
-        for j in range(self.m):
-            for w in range(32):
-                acc = self.o.add_xyzt(acc, self.tabs[j, w][kb[lo:hi, j, w]])
-        return acc
-
-    def __call__(self, k):
-        n = k.shape[0] // self.m
-        kb = self.o.fr_from_bytes_mod_order(k).reshape(n, self.m, 32)
-        bounds = np.linspace(0, n, THREADS + 1).astype(int)
-        with ThreadPoolExecutor(THREADS) as ex:
-            parts = list(ex.map(lambda t: self._part(kb, bounds[t], bounds[t + 1]), range(THREADS)))
-        acc = np.concatenate(parts)
-        return self.o.compress(acc), acc

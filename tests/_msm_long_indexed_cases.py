@@ -3,7 +3,8 @@ Z = 0 record, index arrays with the planted absent terms, and the gather materia
 oracle's fold (tests/_batch_msm_long_cases.py)."""
 import numpy as np
 
-from _batch_msm_long_cases import R, _scalar_bytes, plan
+from _batch_msm_long_cases import plan
+from _sums_support import R, scalar_bytes as _scalar_bytes
 
 POOL = 23
 DEAD_RECORD = 5

@@ -1,15 +1,12 @@
 """Many multiscalar sums of 9 .. 4096 terms on the MI355X (d377_batch_msm_long[_encoded]) against the oracle's fold, on both
 routes of the chains (a wave / a lane per partial sum), against the library's own oracle-checked calls, and through the
 C++ mirror.  The planted cases and the oracle's fold are those of tests/_batch_msm_long_cases.py."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from _batch_msm_long_cases import make_case, oracle_fold, plan
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _sums_support import build_and_run_cpp
 
 pytestmark = pytest.mark.gpu
 
@@ -176,11 +173,4 @@ def test_torch_tensors_are_staged_through_host_memory(ctx, oracle):
 
 def test_cpp_mirror_batch_msm_long():
     """tests/cpp/batch_msm_long.cpp: msm_long through include/decaf377_amd.hpp against the fold of the mirror's own * and +."""
-    from decaf377_amd import _native
-    libdir = os.path.dirname(_native.LIB_PATH)
-    exe = os.path.join(ROOT, "tests", "cpp", "batch_msm_long")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "batch_msm_long.cpp"), "-o", exe, "-L" + libdir, "-ldecaf377_amd",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CPP_BATCH_MSM_LONG_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    build_and_run_cpp("batch_msm_long", "CPP_BATCH_MSM_LONG_OK")

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from _batch_msm_long_cases import make_case, oracle_fold, plan
+from _oracle import _p
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
@@ -26,10 +27,6 @@ FOLD = 16
 # (m, n): 9 = g 2, b 5, one padded slot; 16 = exact groups; 17 = g 3, b 6; 129 = g 17, the second fold level at 16 records per
 # lane; 2049 = g 257, the third
 CASES = [(9, 7), (16, 7), (17, 7), (64, 7), (65, 7), (129, 2), (2049, 1)]
-
-
-def _p(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 @pytest.fixture(scope="module")

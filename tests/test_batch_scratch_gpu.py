@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from _batch_msm_long_cases import make_case, oracle_fold, plan
-from test_msm_mixed_gpu import Fold, _case, _join, _var_terms
+from _sums_support import Fold, join as _join, mixed_case as _case, var_terms as _var_terms
 
 pytestmark = pytest.mark.gpu
 
@@ -45,7 +45,7 @@ def test_three_units_grow_one_table_scratch(oracle):
     bad = np.zeros(N * v, bool)
     bad[::5] = True
     encs[bad] = 0xFF                                             # above q: no canonical Encoding
-    want2 = _join(oracle, Fold(oracle, bases)(idx, fk), _var_terms(oracle, pts, vk, N, v), ~bad.reshape(N, v))
+    want2 = _join(oracle, Fold(oracle, bases).records(idx, fk), _var_terms(oracle, pts, vk, N, v), ~bad.reshape(N, v))
 
     n3, m3 = 37, 17
     assert plan(m3)[1] > v                                       # a group's terms exceed the mixed sums' v: step 3 really grows

@@ -5,18 +5,15 @@ projective records; the library's own width at 129 and 4097 terms against d377_b
 against the host forms; refusals on a live context; the Python routing; a captured graph that outlives the workspace it saw; a
 device listed twice; the C++ mirror.  Every case is a few thousand terms at the most."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from _bucket_sums_cases import WALK, assert_boundary_sums_cover, make_case, oracle_fold, passes, sums_per_pass, window_rule
-from test_msm_long_resident_gpu import Side
+from _sums_support import Side, build_and_run_cpp
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG = -2
 
 
@@ -268,11 +265,4 @@ def test_device_listed_twice_slices_the_sums(oracle):
 
 
 def test_cpp_mirror_bucket_sums():
-    from decaf377_amd import _native
-    libdir = os.path.dirname(_native.LIB_PATH)
-    exe = os.path.join(ROOT, "tests", "cpp", "bucket_sums")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "bucket_sums.cpp"), "-o", exe, "-L" + libdir, "-ldecaf377_amd",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CPP_BUCKET_SUMS_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    build_and_run_cpp("bucket_sums", "CPP_BUCKET_SUMS_OK", hip_headers=True)

@@ -16,6 +16,7 @@ import pytest
 
 from _bucket_sums_cases import (MAX_TERMS, WALK, assert_boundary_sums_cover, key, make_case, oracle_fold, passes, sums_per_pass, window_rule,
                                 windows)
+from _oracle import _p
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
@@ -27,10 +28,6 @@ FIELDS = ("W", "nb", "sums", "pw", "wide_digits", "packed", "tree", "ws_depth", 
           "top_stride", "wsb_lds", "count_parts", "count_nbr", "hist_bytes", "bytes", "c", "scan_chunks", "S", "per", "max_segs", "span_lanes_max")
 CONSTS = ("PT_WORDS", "NODE_STRIDE", "R_NODES", "R_SUMS", "R_BUCKETS", "R_DIGITS", "R_IDX", "R_PTS", "R_CHUNKS", "R_FOLD0", "R_FOLD1", "R_MID")
 KIB = 1024
-
-
-def _p(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 @pytest.fixture(scope="module")

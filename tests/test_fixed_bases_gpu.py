@@ -5,76 +5,16 @@ The oracle's fold for a large batch of sums over FIXED bases is computed the way
 law: k B = sum_w (byte w of k mod r) 256^w B, the 32 x 256 multiples of each base made once by oracle additions and
 doublings and every term folded by oracle additions -- the same values as scalar_mul_xyzt, 10x cheaper, and the encodings
 are canonical, so they compare byte for byte."""
-import ctypes
-import os
-import subprocess
 import threading
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-R = 2111115437357092606062206234695386632838870926408408195193685246394721360383
+from _sums_support import Fold, build_and_run_cpp, planted_scalars as _scalars, random_bases as _bases
+
 WIDTHS = [8, 12, 16, 18]
-THREADS = 16
 
 pytestmark = pytest.mark.gpu
-
-
-def _scalar_bytes(v):
-    return np.frombuffer(int(v).to_bytes(32, "little"), np.uint8)
-
-
-def _scalars(rng, n, m):
-    k = rng.integers(0, 256, (n * m, 32), dtype=np.uint8)
-    for t, v in enumerate([0, 1, R - 1, R, (1 << 256) - 1]):
-        k[(7 * t + 3) % (n * m)] = _scalar_bytes(v)
-    k[:m] = _scalar_bytes((1 << 256) - 1)
-    return k
-
-
-class Fold:
-    """The oracle's sums over fixed bases: byte tables of every base, folds by oracle additions on THREADS threads."""
-
-    def __init__(self, oracle, bases):
-        self.o = oracle
-        self.m = bases.shape[0]
-        ident = oracle.identity_xyzt()
-        tabs = np.zeros((self.m, 32, 256, 16), np.uint64)
-        p = np.ascontiguousarray(bases, dtype=np.uint64)
-        for w in range(32):
-            acc = np.tile(ident, (self.m, 1))
-            for b in range(256):
-                tabs[:, w, b] = acc
-                acc = oracle.add_xyzt(acc, p)
-            for _ in range(8):
-                p = oracle.double_xyzt(p)
-        self.tabs = tabs
-
-    def _part(self, kb, lo, hi):
-        n = hi - lo
-        acc = np.tile(self.o.identity_xyzt(), (n, 1))
-        for j in range(self.m):
-            for w in range(32):
-                acc = self.o.add_xyzt(acc, self.tabs[j, w][kb[lo:hi, j, w]])
-        return acc
-
-    def __call__(self, k):
-        n = k.shape[0] // self.m
-        kb = self.o.fr_from_bytes_mod_order(k).reshape(n, self.m, 32)
-        bounds = np.linspace(0, n, THREADS + 1).astype(int)
-        with ThreadPoolExecutor(THREADS) as ex:
-            parts = list(ex.map(lambda t: self._part(kb, bounds[t], bounds[t + 1]), range(THREADS)))
-        acc = np.concatenate(parts)
-        return self.o.compress(acc), acc
-
-
-def _bases(oracle, rng, m):
-    pts = oracle.elligator_map_xyzt(rng.integers(0, 256, (m, 32), dtype=np.uint8))
-    if m >= 3:
-        pts[1] = oracle.generator_xyzt()
-    return np.ascontiguousarray(pts, dtype=np.uint64)
 
 
 @pytest.fixture(scope="module")
@@ -91,7 +31,7 @@ def test_every_width_and_size_against_the_oracle(ctx, oracle, m):
     bases = _bases(oracle, rng, m)
     nmax = 1 << 16
     k = _scalars(rng, nmax, m)
-    want_enc, want_el = Fold(oracle, bases)(k)
+    want_enc, want_el = Fold(oracle, bases).dense(k)
     for bits in WIDTHS:
         with ctx.fixed_bases(bases, comb_bits=bits) as fb:
             assert fb.info()[:2] == (m, bits)
@@ -134,7 +74,7 @@ def test_degenerate_bases(ctx, oracle):
     as_group[1] = ident                                          # what the Z = 0 record stands for
     n = 4097
     k = _scalars(rng, n, bases.shape[0])
-    want_enc, want_el = Fold(oracle, as_group)(k)
+    want_enc, want_el = Fold(oracle, as_group).dense(k)
     for bits in (8, 16):
         with ctx.fixed_bases(bases, comb_bits=bits) as fb:
             enc, el = fb.msm(k, elements=True)
@@ -198,7 +138,7 @@ def test_concurrent_calls_on_one_handle(ctx, oracle):
             t.join()
         assert not errors, errors
     idx = np.arange(0, 20000, 997)
-    assert (want1[idx] == Fold(oracle, b1)(k1.reshape(-1, 3, 32)[idx].reshape(-1, 32))[0]).all()
+    assert (want1[idx] == Fold(oracle, b1).dense(k1.reshape(-1, 3, 32)[idx].reshape(-1, 32))[0]).all()
 
 
 def test_create_destroy_returns_device_memory(ctx, oracle):
@@ -242,7 +182,7 @@ def test_high_level_and_torch_staging(oracle):
     k = rng.integers(0, 256, (2 * 4096, 32), dtype=np.uint8)
     fb = d.FixedBases(d.Element(bases, c), comb_bits=12)
     enc = fb.vartime_multiscalar_mul(d.Fr(k, c))
-    want = Fold(oracle, bases)(k)[0]
+    want = Fold(oracle, bases).dense(k)[0]
     assert (enc.data == want).all()
     t_enc, t_el = fb.msm(torch.from_numpy(k).to("cuda:0"), elements=True)
     assert t_enc.device.type == "cuda" and t_el.device.type == "cuda"
@@ -252,11 +192,4 @@ def test_high_level_and_torch_staging(oracle):
 
 
 def test_cpp_mirror_fixed_bases():
-    from decaf377_amd import _native
-    libdir = os.path.dirname(_native.LIB_PATH)
-    exe = os.path.join(ROOT, "tests", "cpp", "fixed_bases")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "fixed_bases.cpp"),
-                           "-o", exe, "-L" + libdir, "-ldecaf377_amd", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib",
-                           "-L/opt/rocm/lib", "-lamdhip64"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CPP_FIXED_BASES_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    build_and_run_cpp("fixed_bases", "CPP_FIXED_BASES_OK")

@@ -12,15 +12,12 @@ import subprocess
 import numpy as np
 import pytest
 
+from _sums_support import _p, host_bases as _bases, host_scalars as _scalars
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
 CSRC = os.path.join(ROOT, "decaf377_amd", "csrc")
-R = 2111115437357092606062206234695386632838870926408408195193685246394721360383
 NEW_SYMBOLS = ["d377_fixed_bases_create", "d377_fixed_bases_info", "d377_fixed_bases_destroy", "d377_batch_fixed_msm"]
-
-
-def _p(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 @pytest.fixture(scope="module")
@@ -43,43 +40,6 @@ def libpath():
         import __graft_entry__ as g
         g.build_native()
     return _native.LIB_PATH
-
-
-def _scalar_bytes(v):
-    return np.frombuffer(int(v).to_bytes(32, "little"), np.uint8)
-
-
-def _scalars(rng, n, m):
-    """n x m scalars, term-major within a sum: random 32-byte strings with 0, 1, r - 1, r and 2^256 - 1 spread over them."""
-    k = rng.integers(0, 256, (n * m, 32), dtype=np.uint8)
-    for t, v in enumerate([0, 1, R - 1, R, (1 << 256) - 1]):
-        for j in range(m):
-            k[(t * m + j * (t + 1)) % (n * m)] = _scalar_bytes(v)
-    k[:m] = _scalar_bytes(R - 1)                                  # the first sum: every term r - 1
-    return k
-
-
-def _bases(oracle, rng, m):
-    """m bases: random Elligator outputs, the identity, GENERATOR, a representative with Z != 1 and one that differs from
-    its point by the 2-torsion point (0, -1)."""
-    pts = oracle.elligator_map_xyzt(rng.integers(0, 256, (m + 2, 32), dtype=np.uint8))
-    out = [pts[0]]
-    kinds = ["identity", "generator", "scaled", "torsion"]
-    for j in range(1, m):
-        kind = kinds[(j - 1) % len(kinds)]
-        if kind == "identity":
-            out.append(oracle.identity_xyzt())
-        elif kind == "generator":
-            out.append(oracle.generator_xyzt())
-        elif kind == "scaled":                                      # (lX, lY, lZ, lT): the same point, Z != 1
-            p = pts[j].reshape(4, 4)
-            lam = np.tile(oracle.elligator_map_xyzt(rng.integers(0, 256, (1, 32), dtype=np.uint8))[0][:4], (4, 1))
-            out.append(oracle.fq_op(2, p, lam)[0].reshape(16))
-        else:                                                      # (-X, -Y, Z, T) = P + (0, -1)
-            p = pts[j].reshape(4, 4).copy()
-            p[:2] = oracle.fq_op(4, p[:2])[0]
-            out.append(p.reshape(16))
-    return np.ascontiguousarray(np.stack(out), dtype=np.uint64)
 
 
 def _fold(oracle, bases, k, n, m):

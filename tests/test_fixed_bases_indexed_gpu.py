@@ -6,77 +6,16 @@ The oracle side is the byte-table fold of tests/test_fixed_bases_gpu.py (k B = s
 picking the table of base_index[i, j] for term j; an absent term adds entry 0, the identity.  One fold per (m, t), at the
 largest n, serves every comb width and every smaller n."""
 import ctypes
-import os
-import subprocess
 import threading
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-R = 2111115437357092606062206234695386632838870926408408195193685246394721360383
-THREADS = 16
+from _sums_support import R, Fold, build_and_run_cpp, planted_scalars as _scalars, random_bases as _bases, scalar_bytes as _scalar_bytes
+
 SIZES = (1, 63, 257, 4097)
 
 pytestmark = pytest.mark.gpu
-
-
-def _scalar_bytes(v):
-    return np.frombuffer(int(v).to_bytes(32, "little"), np.uint8)
-
-
-def _scalars(rng, n, m):
-    k = rng.integers(0, 256, (n * m, 32), dtype=np.uint8)
-    for t, v in enumerate([0, 1, R - 1, R, (1 << 256) - 1]):
-        k[(7 * t + 3) % (n * m)] = _scalar_bytes(v)
-    k[:m] = _scalar_bytes((1 << 256) - 1)
-    return k
-
-
-class Fold:
-    """The oracle's indexed sums over fixed bases: byte tables of every base, folds by oracle additions on THREADS threads."""
-
-    def __init__(self, oracle, bases):
-        self.o = oracle
-        self.m = bases.shape[0]
-        ident = oracle.identity_xyzt()
-        tabs = np.zeros((self.m, 32, 256, 16), np.uint64)
-        p = np.ascontiguousarray(bases, dtype=np.uint64)
-        for w in range(32):
-            acc = np.tile(ident, (self.m, 1))
-            for b in range(256):
-                tabs[:, w, b] = acc
-                acc = oracle.add_xyzt(acc, p)
-            for _ in range(8):
-                p = oracle.double_xyzt(p)
-        self.tabs = tabs
-
-    def _part(self, idx, kb, lo, hi):
-        acc = np.tile(self.o.identity_xyzt(), (hi - lo, 1))
-        for j in range(idx.shape[1]):
-            comb = idx[lo:hi, j]
-            for w in range(32):
-                acc = self.o.add_xyzt(acc, self.tabs[comb, w, kb[lo:hi, j, w]])
-        return acc
-
-    def __call__(self, idx, k):
-        n, t = idx.shape
-        kb = self.o.fr_from_bytes_mod_order(k).reshape(n, t, 32).copy()
-        kb[idx < 0] = 0                                          # an absent term: entry 0 of comb 0, the identity
-        comb = np.maximum(idx, 0)
-        bounds = np.linspace(0, n, THREADS + 1).astype(int)
-        with ThreadPoolExecutor(THREADS) as ex:
-            parts = list(ex.map(lambda q: self._part(comb, kb, bounds[q], bounds[q + 1]), range(THREADS)))
-        acc = np.concatenate(parts)
-        return self.o.compress(acc), acc
-
-
-def _bases(oracle, rng, m):
-    pts = oracle.elligator_map_xyzt(rng.integers(0, 256, (m, 32), dtype=np.uint8))
-    if m >= 3:
-        pts[1] = oracle.generator_xyzt()
-    return np.ascontiguousarray(pts, dtype=np.uint64)
 
 
 def _rows(rng, n, t, m, k):
@@ -289,11 +228,4 @@ def test_torch_staging(oracle):
 
 
 def test_cpp_mirror_fixed_bases_indexed():
-    from decaf377_amd import _native
-    libdir = os.path.dirname(_native.LIB_PATH)
-    exe = os.path.join(ROOT, "tests", "cpp", "fixed_bases_indexed")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "fixed_bases_indexed.cpp"), "-o", exe, "-L" + libdir, "-ldecaf377_amd",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CPP_FIXED_BASES_INDEXED_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    build_and_run_cpp("fixed_bases_indexed", "CPP_FIXED_BASES_INDEXED_OK")

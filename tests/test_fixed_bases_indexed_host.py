@@ -13,7 +13,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_fixed_bases_host import R, _bases, _p, _scalar_bytes, _scalars
+from _sums_support import (R, _p, host_bases as _bases, host_scalars as _scalars, indexed_fold_by_scalar_mul as _fold,
+                           scalar_bytes as _scalar_bytes)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
@@ -72,20 +73,6 @@ def _rows(rng, n, t, m, k):
     idx[5, t // 2] = -1
     idx[6, t - 1] = -1
     return idx, 1, cancel
-
-
-def _fold(oracle, bases, idx, k):
-    """The oracle's sums: sum_j k[i t + j] * B_{idx[i, j]} by scalar multiplications and additions; an absent term is
-    0 * identity -> (encodings, records)."""
-    n, t = idx.shape
-    flat = idx.reshape(-1)
-    pts = np.where((flat >= 0)[:, None], bases[np.maximum(flat, 0)], oracle.identity_xyzt()[None, :])
-    kk = np.where((flat >= 0)[:, None], k, 0).astype(np.uint8)
-    terms = oracle.scalar_mul_xyzt(np.ascontiguousarray(pts, dtype=np.uint64), np.ascontiguousarray(kk)).reshape(n, t, 16)
-    acc = np.ascontiguousarray(terms[:, 0])
-    for j in range(1, t):
-        acc = oracle.add_xyzt(acc, np.ascontiguousarray(terms[:, j]))
-    return oracle.compress(acc), acc
 
 
 @pytest.mark.parametrize("bits", [8, 12])

@@ -5,29 +5,14 @@ The cuts are chosen with FixedBases.long_plan, so they happen on whatever CU cou
 two and three fold levels (few sums over many bases), segments of several bases whose last is shorter, and the one segment per
 sum that is d377_batch_fixed_msm's kernel.  The case builders and the oracle's folds are in tests/_fixed_msm_long_cases.py,
 shared with tests/test_fixed_msm_long_host.py."""
-import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from _fixed_msm_long_cases import KINDS, SPECIAL, Fold, levels, make_bases, make_scalars, oracle_fold, plan, scalar_bytes
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _fixed_msm_long_cases import KINDS, SPECIAL, levels, make_bases, make_scalars, oracle_fold, plan
+from _sums_support import Fold, _p, build_and_run_cpp, random_bases as _random_bases, scalar_bytes
 
 pytestmark = pytest.mark.gpu
-
-
-def _p(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
-def _random_bases(oracle, rng, m):
-    pts = oracle.elligator_map_xyzt(rng.integers(0, 256, (m, 32), dtype=np.uint8))
-    if m >= 3:
-        pts[1] = oracle.generator_xyzt()
-    return np.ascontiguousarray(pts, dtype=np.uint64)
 
 
 def _tree_fold(oracle, terms):
@@ -127,7 +112,7 @@ def seg101(ctx, oracle, lanes):
     with ctx.fixed_bases_long(bases, comb_bits=12) as fb:
         assert fb.long_plan(n) == (g, b)
         enc, el = fb.msm_long(k, elements=True)
-    want_enc, want_el = Fold(oracle, bases)(k)
+    want_enc, want_el = Fold(oracle, bases).dense(k)
     return dict(n=n, g=g, b=b, m=m, bases=bases, k=k, enc=enc, el=el, want_enc=want_enc, want_el=want_el)
 
 
@@ -260,14 +245,7 @@ def test_torch_tensors_are_staged_through_host_memory(ctx, oracle):
 
 
 def test_cpp_mirror_fixed_bases_long():
-    from decaf377_amd import _native
-    libdir = os.path.dirname(_native.LIB_PATH)
-    exe = os.path.join(ROOT, "tests", "cpp", "fixed_bases_long")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "fixed_bases_long.cpp"), "-o", exe, "-L" + libdir, "-ldecaf377_amd",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CPP_FIXED_BASES_LONG_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    build_and_run_cpp("fixed_bases_long", "CPP_FIXED_BASES_LONG_OK")
 
 
 def test_context_health_afterwards(ctx):

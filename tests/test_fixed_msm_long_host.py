@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from _fixed_msm_long_cases import levels, make_bases, make_scalars, oracle_fold, plan
+from _oracle import _p
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
@@ -28,10 +29,6 @@ NAMES = ("d377_fixed_bases_create_long", "d377_batch_fixed_long_msm", "d377_fixe
 CASES = {(1, 6, 1000): (1, 1), (5, 6, 6): (5, 1), (9, 4, 8): (5, 2), (17, 3, 51): (1, 17), (101, 2, 52): (4, 26),
          (257, 2, 514): (1, 257)}
 SAN_CASE = (101, 2, 52)
-
-
-def _p(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _stale(out):

@@ -19,6 +19,7 @@ import pytest
 
 from _batch_msm_long_cases import oracle_fold, plan
 from _msm_long_indexed_cases import DEAD_RECORD, POOL, make_indexed, make_pool, materialise
+from _oracle import _p
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
@@ -29,10 +30,6 @@ NAMES = {"d377_batch_long_msm_resident": 9, "d377_batch_long_msm_encoded_residen
 # 4096 = g 512, three
 CASES = [(1, 3), (8, 3), (9, 3), (17, 3), (129, 3), (4096, 1)]
 ERR_ARG = -2
-
-
-def _p(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 @pytest.fixture(scope="module")

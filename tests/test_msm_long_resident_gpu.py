@@ -8,18 +8,16 @@ The plain cases are make_case's (tests/_batch_msm_long_cases.py: planted scalars
 ones tests/_msm_long_indexed_cases.py's: a pool of 23 points with record 5 at Z = 0, indices 0 and 22, repeats, and absent
 terms -- a whole group, a whole sum, the last term of a sum."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from _batch_msm_long_cases import make_case, oracle_fold, plan
 from _msm_long_indexed_cases import DEAD_RECORD, POOL, make_indexed, make_pool, materialise
+from _sums_support import Side, build_and_run_cpp
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NONE = (1 << 64) - 1
 ERR_ARG = -2
 
@@ -37,40 +35,6 @@ def ctx():
     yield c
     assert c.health()[0] == 0 and c.health()[2] == 0             # after the file's tests: no lane set claimed, nobody gave up
     c.close()
-
-
-class Side:
-    """Device copies of host arrays and the resident calls on ONE side stream; host() synchronises that stream alone."""
-
-    def __init__(self, torch, ctx):
-        self.torch, self.ctx, self.lib = torch, ctx, ctx._lib
-        self.stream = torch.cuda.Stream(device="cuda:0")
-
-    def dev(self, a):
-        a = np.ascontiguousarray(a)
-        t = self.torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to("cuda:0")
-        self.torch.cuda.current_stream().synchronize()           # the copy is done before the side stream reads it
-        return t
-
-    def empty(self, shape, kind="u8", fill=None):
-        dt = {"u8": self.torch.uint8, "u64": self.torch.int64}[kind]
-        t = self.torch.empty(shape, dtype=dt, device="cuda:0") if fill is None else self.torch.full(shape, fill, dtype=dt, device="cuda:0")
-        self.torch.cuda.current_stream().synchronize()
-        return t
-
-    def call(self, name, *args, stream=None):
-        conv = [ctypes.c_void_p(a.data_ptr()) if hasattr(a, "data_ptr") else a for a in args]
-        s = self.stream.cuda_stream if stream is None else stream
-        return getattr(self.lib, name)(self.ctx._h, 0, ctypes.c_void_p(s), *conv)
-
-    def ok(self, name, *args, stream=None):
-        rc = self.call(name, *args, stream=stream)
-        assert rc == 0, (name, rc, self.lib.d377_last_error().decode())
-
-    def host(self, t):
-        self.stream.synchronize()
-        a = t.cpu().numpy()
-        return a.view(np.uint64) if a.dtype == np.int64 else a
 
 
 @pytest.fixture(scope="module")
@@ -376,11 +340,4 @@ def test_graph_replays_and_outlives_the_scratch_it_saw(torch, oracle, pool):
 
 
 def test_cpp_mirror_msm_long_indexed():
-    from decaf377_amd import _native
-    libdir = os.path.dirname(_native.LIB_PATH)
-    exe = os.path.join(ROOT, "tests", "cpp", "msm_long_indexed")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "msm_long_indexed.cpp"), "-o", exe, "-L" + libdir, "-ldecaf377_amd",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CPP_MSM_LONG_INDEXED_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    build_and_run_cpp("msm_long_indexed", "CPP_MSM_LONG_INDEXED_OK", hip_headers=True)

@@ -6,136 +6,16 @@ The oracle side: the variable terms by scalar_mul_xyzt, the fixed part by the by
 tests/test_fixed_bases_indexed_gpu.py (restated here: k B = sum_w (byte w of k mod r) 256^w B), everything joined by add_xyzt.
 One fold per shape, at the largest n, kept as the fixed sums and the separate variable terms, serves every smaller n and the
 Encoding form (a dropped term is left out of the joining additions)."""
-import ctypes
-import os
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-R = 2111115437357092606062206234695386632838870926408408195193685246394721360383
-THREADS = 16
+from _sums_support import (ABSENT, CANCEL, VZERO, Fold, _p, build_and_run_cpp, join as _join, mixed_case as _case, random_bases as _bases,
+                           var_terms as _var_terms)
+
 SIZES = (1, 63, 257, 2049)                                       # straddle one workgroup of BLOCK = 256 lanes
 SHAPES = [(1, 1, 1, 16), (1, 1, 1, 18), (1, 2, 64, 12), (3, 2, 5, 8), (8, 3, 5, 12), (2, 64, 64, 8)]   # (v, t, m, bits)
-ZROW, ABSENT, VZERO, DOUBLE, CANCEL = 10, 11, 12, 13, 14           # the planted sums, within the first 63 (sum 0: see _case)
 
 pytestmark = pytest.mark.gpu
-
-
-def _p(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
-def _scalar_bytes(v):
-    return np.frombuffer(int(v).to_bytes(32, "little"), np.uint8)
-
-
-def _scalars(rng, n, m):
-    k = rng.integers(0, 256, (n * m, 32), dtype=np.uint8)
-    for t, v in enumerate([0, 1, R - 1, R, (1 << 256) - 1]):
-        k[(7 * t + 3) % (n * m)] = _scalar_bytes(v)
-    k[:m] = _scalar_bytes((1 << 256) - 1)
-    return k
-
-
-def _threaded(f, n):
-    """f(lo, hi) on THREADS slices of 0 .. n, concatenated (the oracle's calls release the interpreter lock)."""
-    bounds = np.linspace(0, n, THREADS + 1).astype(int)
-    with ThreadPoolExecutor(THREADS) as ex:
-        return np.concatenate(list(ex.map(lambda q: f(bounds[q], bounds[q + 1]), range(THREADS))))
-
-
-class Fold:
-    """The oracle's indexed sums over fixed bases: byte tables of every base, folds by oracle additions on THREADS threads
-    (tests/test_fixed_bases_indexed_gpu.py's, returning the records)."""
-
-    def __init__(self, oracle, bases):
-        self.o = oracle
-        self.m = bases.shape[0]
-        ident = oracle.identity_xyzt()
-        tabs = np.zeros((self.m, 32, 256, 16), np.uint64)
-        p = np.ascontiguousarray(bases, dtype=np.uint64)
-        for w in range(32):
-            acc = np.tile(ident, (self.m, 1))
-            for b in range(256):
-                tabs[:, w, b] = acc
-                acc = oracle.add_xyzt(acc, p)
-            for _ in range(8):
-                p = oracle.double_xyzt(p)
-        self.tabs = tabs
-
-    def _part(self, idx, kb, lo, hi):
-        acc = np.tile(self.o.identity_xyzt(), (hi - lo, 1))
-        for j in range(idx.shape[1]):
-            comb = idx[lo:hi, j]
-            for w in range(32):
-                acc = self.o.add_xyzt(acc, self.tabs[comb, w, kb[lo:hi, j, w]])
-        return acc
-
-    def __call__(self, idx, k):
-        n, t = idx.shape
-        kb = self.o.fr_from_bytes_mod_order(k).reshape(n, t, 32).copy()
-        kb[idx < 0] = 0                                          # an absent term: entry 0 of comb 0, the identity
-        comb = np.maximum(idx, 0)
-        return _threaded(lambda lo, hi: self._part(comb, kb, lo, hi), n)
-
-
-def _bases(oracle, rng, m):
-    pts = oracle.elligator_map_xyzt(rng.integers(0, 256, (m, 32), dtype=np.uint8))
-    if m >= 3:
-        pts[1] = oracle.generator_xyzt()
-    return np.ascontiguousarray(pts, dtype=np.uint64)
-
-
-def _var_terms(oracle, pts, vk, n, v):
-    """[n, v, 16]: the oracle's k P of every variable term; a record with Z = 0 counts as the identity."""
-    q = pts.copy()
-    q[~q[:, 8:12].any(1)] = oracle.identity_xyzt()
-    return _threaded(lambda lo, hi: oracle.scalar_mul_xyzt(np.ascontiguousarray(q[lo:hi]), np.ascontiguousarray(vk[lo:hi])),
-                     n * v).reshape(n, v, 16)
-
-
-def _join(oracle, fixed, terms, live=None):
-    """fixed sums + the variable terms (those with live[i, p] false left out) -> (encodings, records)."""
-    acc = np.ascontiguousarray(fixed)
-    ident = oracle.identity_xyzt()
-    for p in range(terms.shape[1]):
-        tp = np.ascontiguousarray(terms[:, p])
-        if live is not None:
-            tp = np.where(live[:, p, None], tp, ident[None, :])
-        acc = oracle.add_xyzt(acc, np.ascontiguousarray(tp, dtype=np.uint64))
-    return oracle.compress(acc), acc
-
-
-def _case(oracle, v, t, m, n, seed=0):
-    """Bases, index rows, scalars and points of n sums with the planted rows of tests/test_msm_mixed_host.py.  Sum 0 (all that
-    n = 1 sees) has the largest scalars on both sides and its last fixed term absent when t > 1."""
-    rng = np.random.default_rng(1000 * v + 10 * t + m + seed)
-    bases = _bases(oracle, rng, m)
-    fk, vk = _scalars(rng, n, t), _scalars(rng, n, v)
-    idx = rng.integers(0, m, (n, t)).astype(np.int32)
-    idx[rng.random((n, t)) < 0.1] = -1
-    idx[0] = m - 1
-    if t > 1:
-        idx[0, t - 1] = -1
-    idx[2] = 1 % m                                               # one index repeated
-    pts = np.ascontiguousarray(oracle.elligator_map_xyzt(rng.integers(0, 256, (n * v, 32), dtype=np.uint8)), dtype=np.uint64)
-    if n > CANCEL:
-        pts[5 * v] = oracle.identity_xyzt()
-        pts[ZROW * v, 8:12] = 0                                  # a record with Z = 0
-        idx[ABSENT] = -1                                         # no fixed term: the variable sum alone
-        vk[VZERO * v:(VZERO + 1) * v] = 0                        # every variable scalar 0: the fixed sum alone
-        kv = int.from_bytes(rng.integers(0, 256, 32, dtype=np.uint8).tobytes(), "little") % R
-        for row, other in ((DOUBLE, kv), (CANCEL, R - kv)):      # P_0 = B_0 meets the fixed term on base 0: doubling, cancelling
-            idx[row] = -1
-            idx[row, t - 1] = 0
-            fk[row * t + t - 1] = _scalar_bytes(kv)
-            vk[row * v:(row + 1) * v] = 0
-            vk[row * v] = _scalar_bytes(other)
-            pts[row * v] = bases[0]
-    return bases, np.ascontiguousarray(idx), fk, pts, vk
 
 
 @pytest.fixture(scope="module")
@@ -155,7 +35,7 @@ def folds(oracle):
         if (v, t, m) not in made:
             n = SIZES[-1]
             bases, idx, fk, pts, vk = _case(oracle, v, t, m, n)
-            made[(v, t, m)] = (bases, idx, fk, pts, vk, Fold(oracle, bases)(idx, fk), _var_terms(oracle, pts, vk, n, v))
+            made[(v, t, m)] = (bases, idx, fk, pts, vk, Fold(oracle, bases).records(idx, fk), _var_terms(oracle, pts, vk, n, v))
         return made[(v, t, m)]
     return get
 
@@ -216,7 +96,7 @@ def test_smallest_multi_round_chunk(ctx, oracle):
     vk = rng.integers(0, 256, (n, 32), dtype=np.uint8)
     pts = np.ascontiguousarray(oracle.elligator_map_xyzt(rng.integers(0, 256, (n, 32), dtype=np.uint8)), dtype=np.uint64)
     idx = np.zeros((n, 1), np.int32)
-    fixed = Fold(oracle, base)(idx, fk)
+    fixed = Fold(oracle, base).records(idx, fk)
     want = _join(oracle, fixed, _var_terms(oracle, pts, vk, n, 1))[0]
     with ctx.fixed_bases(base, comb_bits=16) as fb:
         enc = fb.msm_mixed(idx, fk, pts, vk)
@@ -239,7 +119,7 @@ def test_long_handle_with_its_last_base_in_use(ctx, oracle):
     bases, idx, fk, pts, vk = _case(oracle, v, t, m, n)
     idx[:, 0] = 64                                               # past what a short registration holds
     idx[ABSENT, 0] = -1
-    want = _join(oracle, Fold(oracle, bases)(idx, fk), _var_terms(oracle, pts, vk, n, v))[0]
+    want = _join(oracle, Fold(oracle, bases).records(idx, fk), _var_terms(oracle, pts, vk, n, v))[0]
     with ctx.fixed_bases_long(bases, comb_bits=8) as fb:
         enc = fb.msm_mixed(idx, fk, pts, vk)
     assert (enc == want).all(), np.nonzero((enc != want).any(1))[0][:8]
@@ -327,11 +207,4 @@ def test_health_afterwards(ctx):
 
 
 def test_cpp_mirror_msm_mixed():
-    from decaf377_amd import _native
-    libdir = os.path.dirname(_native.LIB_PATH)
-    exe = os.path.join(ROOT, "tests", "cpp", "msm_mixed")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "msm_mixed.cpp"), "-o", exe, "-L" + libdir, "-ldecaf377_amd",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CPP_MSM_MIXED_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    build_and_run_cpp("msm_mixed", "CPP_MSM_MIXED_OK")

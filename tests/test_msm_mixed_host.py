@@ -21,8 +21,8 @@ import sys
 import numpy as np
 import pytest
 
-from test_fixed_bases_host import R, _bases, _p, _scalar_bytes, _scalars
-from test_fixed_bases_indexed_host import _fold as _fixed_fold
+from _sums_support import (R, _p, host_bases as _bases, host_scalars as _scalars, indexed_fold_by_scalar_mul as _fixed_fold,
+                           scalar_bytes as _scalar_bytes)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIM_DIR = os.path.join(ROOT, "tests", "host_sim")

@@ -4,7 +4,7 @@ d377_check_base_index_resident, called through the C ABI on torch tensors, each 
 
 Every resident call is compared with its host form on the same inputs -- equal Encodings and status bytes, Elements equal
 under the oracle's eq_xyzt and compressing to their Encodings -- and one shape per call with the oracle's fold directly.  The
-cases and the folds are those of tests/_batch_msm_long_cases.py, tests/_fixed_msm_long_cases.py and tests/test_msm_mixed_gpu.py.
+cases and the folds are those of tests/_batch_msm_long_cases.py, tests/_fixed_msm_long_cases.py and tests/_sums_support.py.
 n = 257 is two workgroups of 256 lanes with one live lane in the second.
 
 The index verdict: one record per call, (refused indices, first position or UINT64_MAX); a refused index contributes nothing.
@@ -18,7 +18,7 @@ import pytest
 
 import _fixed_msm_long_cases as fl
 from _batch_msm_long_cases import make_case, oracle_fold, plan
-from test_msm_mixed_gpu import Fold, _case, _join, _var_terms
+from _sums_support import Fold, Side, build_and_run_cpp, join as _join, mixed_case as _case, var_terms as _var_terms
 
 pytestmark = pytest.mark.gpu
 
@@ -40,41 +40,6 @@ def ctx():
     c = d.Context([0], comb_lazy=True)
     yield c
     c.close()
-
-
-class Side:
-    """Device copies of host arrays and the resident calls on ONE side stream; host() synchronises that stream alone."""
-
-    def __init__(self, torch, ctx):
-        self.torch, self.ctx, self.lib = torch, ctx, ctx._lib
-        self.stream = torch.cuda.Stream(device="cuda:0")
-
-    def dev(self, a):
-        a = np.ascontiguousarray(a)
-        t = self.torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to("cuda:0")
-        self.torch.cuda.current_stream().synchronize()           # the copy is done before the side stream reads it
-        return t
-
-    def empty(self, shape, kind="u8", fill=None):
-        dt = {"u8": self.torch.uint8, "u64": self.torch.int64}[kind]
-        t = self.torch.empty(shape, dtype=dt, device="cuda:0") if fill is None else self.torch.full(shape, fill, dtype=dt, device="cuda:0")
-        self.torch.cuda.current_stream().synchronize()
-        return t
-
-    def call(self, name, *args, stream=None):
-        """rc of the resident call `name`: (ctx, dev 0, the side stream, *args), tensors passed as their device pointers."""
-        conv = [ctypes.c_void_p(a.data_ptr()) if hasattr(a, "data_ptr") else a for a in args]
-        s = self.stream.cuda_stream if stream is None else stream
-        return getattr(self.lib, name)(self.ctx._h, 0, ctypes.c_void_p(s), *conv)
-
-    def ok(self, name, *args, stream=None):
-        rc = self.call(name, *args, stream=stream)
-        assert rc == 0, (name, rc, self.lib.d377_last_error().decode())
-
-    def host(self, t):
-        self.stream.synchronize()
-        a = t.cpu().numpy()
-        return a.view(np.uint64) if a.dtype == np.int64 else a
 
 
 @pytest.fixture(scope="module")
@@ -209,7 +174,7 @@ def mixed325(oracle):
     """(v, t, bases) = (3, 2, 5) at n = 257 with the oracle's fixed sums and variable terms, made once."""
     v, t, m = 3, 2, 5
     bases, idx, fk, pts, vk = _case(oracle, v, t, m, N)
-    return bases, idx, fk, pts, vk, Fold(oracle, bases)(idx, fk), _var_terms(oracle, pts, vk, N, v)
+    return bases, idx, fk, pts, vk, Fold(oracle, bases).records(idx, fk), _var_terms(oracle, pts, vk, N, v)
 
 
 def test_mixed_signature_shape(ctx, side, oracle):
@@ -503,14 +468,4 @@ def test_graph_replays_and_outlives_the_scratch_it_saw(torch, oracle, mixed325):
 
 
 def test_cpp_mirror_resident_sums():
-    import os
-    import subprocess
-    from decaf377_amd import _native
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    libdir = os.path.dirname(_native.LIB_PATH)
-    exe = os.path.join(root, "tests", "cpp", "resident_sums")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(root, "include"),
-                           os.path.join(root, "tests", "cpp", "resident_sums.cpp"), "-o", exe, "-L" + libdir, "-ldecaf377_amd",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CPP_RESIDENT_SUMS_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    build_and_run_cpp("resident_sums", "CPP_RESIDENT_SUMS_OK", hip_headers=True)
