@@ -1,5 +1,5 @@
 // batch_host.hpp -- the host launch path the batched-sum units share (batch_msm.hip, batch_msm_long.hip,
-// batch_msm_long_indexed.hip, batch_msm_mixed.hip, fixed_bases.hip): the residency check of a lane kernel, the Straus table scratch, the chunk deal of a lane-set kernel and
+// batch_msm_long_indexed.hip, batch_msm_mixed.hip, fixed_bases.hip): the residency check of a lane kernel, the Straus table scratch, the DcbScratch of a lane-set kernel's chunk deal (launch_plan.hpp) and
 // the frame of one device's slice of a host-pointer call.  (The fan-out over the devices is host_state.hpp's
 // slice_over_devices.)  Everything here runs under ctx->mu.
 #pragma once
@@ -61,16 +61,23 @@ inline int straus_scratch_reserve(DeviceState& d, hipStream_t s, size_t terms, c
   return D377_OK;
 }
 
-// The chunks of a lane-set kernel over `count` elements (deal_chunks), at most kmax rounds per chunk: the launch's grid and
-// its DcbScratch.  A launch of at most two generations of workgroups asks for issue priority by progress (dcb.hpp), as
-// d377.hip's chunks_of.
-inline DcbScratch lane_chunks(const DeviceState& d, size_t count, int* grid, int kmax = DCB_K) {
-  const size_t places = (size_t)d.cus * WAVES_PER_SIMD;
-  const ChunkDeal c = deal_chunks((count + BLOCK - 1) / BLOCK, places, (size_t)kmax, (size_t)d.cus * 64);
-  DcbScratch dcb{d.dcb_scratch, d.slot_pool, d.cus * WAVES_PER_SIMD, (int)c.per_lane, d.dcb_sets * BLOCK, (int)c.extra, d.pool_health};
-  dcb.prio = c.nchunks <= 2 * places ? 1 : 0;
-  *grid = (int)c.nchunks;
+// launch_plan.hpp restates these (it is compiled without the device headers)
+static_assert(PLAN_BLOCK == BLOCK && PLAN_WAVES_PER_SIMD == WAVES_PER_SIMD && PLAN_DCB_K == DCB_K && PLAN_DCB_KMAX == DCB_KMAX &&
+              PLAN_DCB_K_LONG == DCB_K_LONG && PLAN_FB_SETS == FB_SETS && PLAN_FB_K == FB_K && PLAN_FB_WIDE_GENERATIONS == FB_WIDE_GENERATIONS,
+              "launch_plan.hpp");
+
+// The DcbScratch of a lane-set launch: the device's areas around the numbers of the plan's chunk deal (launch_plan.hpp).
+inline DcbScratch lane_scratch(const DeviceState& d, const LaneDeal& c) {
+  DcbScratch dcb{d.dcb_scratch, d.slot_pool, c.nslots, c.per_lane, d.dcb_sets * BLOCK, c.extra, d.pool_health};
+  dcb.prio = c.prio;
   return dcb;
+}
+// The chunks of a lane-set kernel of the sums over `count` elements, at most kmax rounds per chunk: the launch's grid and its
+// DcbScratch (lane_deal, the form that reads no tuning key).
+inline DcbScratch lane_chunks(const DeviceState& d, size_t count, int* grid, int kmax = DCB_K) {
+  const LaneDeal c = lane_deal(d, count, WAVES_PER_SIMD, kmax, false);
+  *grid = c.grid;
+  return lane_scratch(d, c);
 }
 
 // One device's slice of a host-pointer call: body() stages the inputs, launches on d.stream and enqueues the copies out; the

@@ -108,11 +108,7 @@ int batch_msm_launch(DeviceState& d, hipStream_t s, bool encoded, const void* pt
                      uint8_t* out32, uint64_t* xyzt_out, uint8_t* status) {
   if (n == 0) return D377_OK;
   const SqrtTables T = d.tables();
-  // up to four sums per SIMD: a wave per sum (the lane kernel needs two sums per lane of the chip before it is the better use of
-  // it: 2^12 three-term sums 1.41 ms on lanes).  D377_TUNE_TINY_MAX, the developer override of every wave-per-element route,
-  // scales this one too.
-  const size_t wave_max = 4 * (size_t)d.tuned(D377_TUNE_TINY_MAX, (long long)d.cus * 4);
-  if (n <= wave_max) {
+  if (n <= sums_wave_max(d)) {                               // up to four sums per SIMD: a wave per sum (launch_plan.hpp)
     const size_t lds = m * row::RQ_TAB_ENTRIES * RQ_WORDS * sizeof(uint32_t);
     if (encoded) hipLaunchKernelGGL(k_batch_msm_wave<true>, dim3((unsigned)n), dim3(64), lds, s, T, pts_in, scalars, (int)m, n, out32, xyzt_out, status);
     else hipLaunchKernelGGL(k_batch_msm_wave<false>, dim3((unsigned)n), dim3(64), lds, s, T, pts_in, scalars, (int)m, n, out32, xyzt_out, status);

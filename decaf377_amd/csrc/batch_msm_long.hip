@@ -182,9 +182,7 @@ int long_sums_fold_compress(DeviceState& d, hipStream_t s, size_t n, size_t g, u
   for (size_t c = g; c > 1; c = fold_out(c)) {
     const size_t oc = fold_out(c), lanes = n * oc;
     uint64_t* dst = (oc == 1 && xyzt_out) ? xyzt_out : half[turn];
-    size_t grid = (lanes + BLOCK - 1) / BLOCK;
-    if (grid > (size_t)d.cus * 8) grid = (size_t)d.cus * 8;
-    hipLaunchKernelGGL(k_msm_long_fold, dim3((unsigned)grid), dim3(BLOCK), 0, s, cur, c, n, dst);
+    hipLaunchKernelGGL(k_msm_long_fold, dim3((unsigned)fold_grid(d, lanes)), dim3(BLOCK), 0, s, cur, c, n, dst);
     HIP_TRY(hipGetLastError());
     cur = dst;
     turn ^= 1;
@@ -215,8 +213,7 @@ int batch_msm_long_launch(DeviceState& d, hipStream_t s, bool encoded, const voi
   if ((rc = long_sums_partials(d, s, n, plan.g, &partials))) return rc;
 
   // ---- phase 1: the chains.  The route by the number of PARTIAL sums, batch_msm.hip's rule: up to four per SIMD a wave each
-  const size_t wave_max = 4 * (size_t)d.tuned(D377_TUNE_TINY_MAX, (long long)d.cus * 4);
-  if (np <= wave_max) {
+  if (np <= sums_wave_max(d)) {                              // (launch_plan.hpp)
     if ((rc = vb.acquire())) return rc;
     const size_t lds = plan.b * row::RQ_TAB_ENTRIES * RQ_WORDS * sizeof(uint32_t);
     if (encoded) hipLaunchKernelGGL(k_msm_long_wave<true>, dim3((unsigned)np), dim3(64), lds, s, T, pts_in, scalars, plan, np, partials, status);

@@ -184,8 +184,7 @@ int batch_msm_long_indexed_launch(DeviceState& d, hipStream_t s, const uint64_t*
   if ((rc = long_sums_partials(d, s, n, plan.g, &partials))) return rc;
 
   // ---- phase 1: the chains, routed as batch_msm_long.hip's: up to four partial sums per SIMD a wave each
-  const size_t wave_max = 4 * (size_t)d.tuned(D377_TUNE_TINY_MAX, (long long)d.cus * 4);
-  if (np <= wave_max) {
+  if (np <= sums_wave_max(d)) {                              // (launch_plan.hpp)
     if ((rc = vb.acquire())) return rc;
     const size_t lds = plan.b * row::RQ_TAB_ENTRIES * RQ_WORDS * sizeof(uint32_t);
     hipLaunchKernelGGL(k_msm_long_indexed_wave, dim3((unsigned)np), dim3(64), lds, s, T, pool, pool_count, point_index, scalars, plan, np,

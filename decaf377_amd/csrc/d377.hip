@@ -24,6 +24,7 @@
 #include "quad_ops.hpp"
 #include "row_ops.hpp"
 #include "host_state.hpp"
+#include "batch_host.hpp"
 #include "codec_chunked.hpp"
 #include "fixed_comb.hpp"
 
@@ -1298,26 +1299,9 @@ int d377::debug_device_delay_ms() {
 
 namespace {
 
-// Batches up to this many elements take the quad-per-element kernel (k_scalar_mul_var_small).  One wave of 16 quads per
-// SIMD is 16 x 4 x CUs elements (16 384); the kernel still wins a little beyond that: the Element form (20 KiB of LDS per
-// wave: seven waves per CU) runs 28 672 elements in one generation, two waves sharing most SIMDs -- 0.60 ms against 0.88
-// with one lane per element -- and the Encoding form (39 KiB: four waves per CU) two generations of 16 384 in 1.02 ms
-// against 1.08.  Beyond those sizes one lane per element is the better use of the chip (measured, profiles/README.md).
-// D377_TUNE_SMALL_MAX: developer override (0 switches the small-batch kernel off).
-size_t small_batch_max(const DeviceState& d, bool element_form) {
-  return (size_t)d.tuned(D377_TUNE_SMALL_MAX, (long long)d.cus * SMALL_QUADS * (element_form ? 7 : 8));
-}
-
-// Batches up to this many elements take one WAVE per element (k_scalar_mul_var_tiny): one wave per SIMD.  Capped by
-// small_batch_max, so that switching the small-batch kernels off switches this one off too.  D377_TUNE_TINY_MAX: developer override.
-size_t tiny_batch_max(const DeviceState& d) {
-  const size_t v = (size_t)d.tuned(D377_TUNE_TINY_MAX, (long long)d.cus * 4), cap = small_batch_max(d, true);
-  return v < cap ? v : cap;
-}
-
-// ... and the square-root family's batches of up to FOUR elements per wave (k_*_tiny above)
-size_t tiny4_batch_max(const DeviceState& d) { return tiny_batch_max(d) * TINY4; }
-unsigned tiny4_grid(size_t n) { return (unsigned)((n + TINY4 - 1) / TINY4); }
+// launch_plan.hpp restates these (it is compiled without the kernels)
+static_assert(PLAN_SMALL_THREADS == SMALL_THREADS && PLAN_SMALL_QUADS == SMALL_QUADS && PLAN_TINY4 == TINY4 &&
+              PLAN_CODEC_CHUNKED_MIN == CODEC_CHUNKED_MIN && PLAN_AFFINE_PER_LANE == AFFINE_PER_LANE, "launch_plan.hpp");
 
 int init_tables(DeviceState& d, uint32_t* keys, int* coll) {
   hipLaunchKernelGGL(k_init_gtab, dim3(6), dim3(BLOCK), 0, d.stream, d.gtab);
@@ -1558,300 +1542,192 @@ void free_device(DeviceState& d) {
 
 // launches one op on device buffers; in0/in1 inputs, out0/out1 outputs (unused ones null).
 // aux: the D377_FQ_* selector of OP_FQ_BIN / OP_FQ_UN / OP_FR_BIN / OP_FR_UN, the D377_SQRT_ROOT_* convention of OP_SQRT.
-// The caller holds ctx->mu (the scratch guards are host state).
+// Which kernel, which grid and how its chunks are dealt is the plan's (launch_plan.hpp: every threshold and its
+// measurements); here the plan meets the device's state and the kernels.  The caller holds ctx->mu (the scratch guards
+// are host state).
 int launch(DeviceState& d, hipStream_t s, Op op, int aux, const void* in0, const void* in1, size_t n, void* out0, void* out1) {
   if (n == 0) return D377_OK;
   const SqrtTables T = d.tables();
-  const int g = grid_of(d, n);
-  // kernels that work in chunks of DCB_K x 256 elements: one workgroup per chunk (oversubscribed on purpose, see
-  // DcbScratch), each claiming one of the vb_blocks resident lane sets of the per-device scratch areas
-  // DCB_K elements per lane when the batch is large enough to fill the resident lane sets that way, fewer otherwise
-  int gv = 0;
-  DcbScratch dcb{};
-  // The batch in rounds of BLOCK elements over the `places` workgroups that are resident at once (cus x sets).  Up to
-  // kmax rounds per place everything runs in ONE generation, and the rounds are dealt out as evenly as they go: every
-  // workgroup takes rounds / places of them and the first rounds % places workgroups one more (DcbScratch::extra).
-  // (Chunks of ceil(n / resident lanes) elements per lane for everybody left a batch just above k x the resident lanes
-  // with fewer workgroups of k + 1 rounds each: pairs of them shared a CU while other CUs held one, and the call took
-  // as long as k + 1 full rounds -- profiles/r04_size_sweep.txt.)  Beyond that: the same deal over the fewest generations
-  // that hold the rounds (host_state.hpp deal_chunks), as many workgroups as chunks (oversubscribed on purpose, see DcbScratch).
-  auto chunks_of = [&](int sets, int kmax, int& grid, DcbScratch& sc) {
-    const size_t places = (size_t)d.cus * (size_t)sets;
-    const size_t rounds = (n + BLOCK - 1) / BLOCK;
-    size_t per_lane, extra = 0, nchunks;
-    if (d.is_tuned(D377_TUNE_CHUNK_PER_LANE)) {                             // developer override (sweeps, route tests): uniform chunks
-      per_lane = (size_t)d.tuned(D377_TUNE_CHUNK_PER_LANE, 1);
-      if (per_lane > (size_t)kmax) per_lane = (size_t)kmax;
-      nchunks = (rounds + per_lane - 1) / per_lane;
-    } else {
-      const ChunkDeal c = deal_chunks(rounds, places, (size_t)kmax, (size_t)d.cus * 64);      // host_state.hpp
-      per_lane = c.per_lane; extra = c.extra; nchunks = c.nchunks;
-    }
-    if (nchunks > (size_t)d.cus * 64) nchunks = (size_t)d.cus * 64;
-    grid = (int)nchunks;
+  LaunchPlan p = launch_plan(op, aux, n, d);
+  // codec_chunked.hip's kernels may claim lane sets only where their residency matches the sets: device state (an occupancy
+  // query on first use), asked on the calls that would take them and on no other
+  if (p.route == ROUTE_CODEC_CHUNKED && !codec_chunked_ok(d)) p = wide_grid_plan(d, n);
+  DcbScratch dcb = lane_scratch(d, p.deal);                  // (batch_host.hpp; all zero on a route without chunks)
 #ifdef D377_DCB_TICKETS                   // A/B only (dcb.hpp): the resident workgroups take the chunks by ticket
-    if ((size_t)grid > places) grid = (int)places;
-#endif
-    sc = DcbScratch{d.dcb_scratch, d.slot_pool, d.cus * sets, (int)per_lane, d.dcb_sets * BLOCK, (int)extra, d.pool_health};
-    // Issue priority by progress (dcb.hpp dcb_progress_priority) for launches of one or two generations of workgroups: there the
-    // workgroups of a CU would end one after the other (-4 to -8 % at 2^20, -1 to -3 % at 1.5 and 2 x 2^20).  Longer launches
-    // refill their CUs and only their last generation has that tail: within +-1 % either way at 2^22, so they stay as they
-    // were measured (profiles/r05_ab_progress_priority.txt).
-    sc.prio = nchunks <= 2 * places ? 1 : 0;
-  };
-  chunks_of(WAVES_PER_SIMD, DCB_K_LONG, gv, dcb);  // every chunked kernel but the fixed-base one (up to 2^20 on 256 CUs: <= DCB_K per lane either way)
-#ifdef D377_DCB_TICKETS
+  if (p.route != ROUTE_EL_UNIFORM && p.deal.nslots && p.grid > p.deal.nslots) {
+    p.grid = p.deal.nslots;
+    if (p.route == ROUTE_FB_WIDE) dcb.prio = p.deal.grid <= 2 * p.deal.nslots ? 1 : 0;    // (one generation: the wide launch's exception never applies)
+  }
   HIP_TRY(hipMemsetAsync(d.pool_health + 3, 0, sizeof(uint32_t), s));      // the launch's chunk counter
 #endif
+  const dim3 g((unsigned)p.grid), b((unsigned)p.block);
   GuardScope vb{d.vb_guard, s};            // released (event recorded) when this function returns, if it was acquired
   int rc;
+  if ((op == OP_MUL_BASE || op == OP_MUL_BASE_EL) && (rc = ensure_comb(d, s))) return rc;   // (a lazy context's first fixed-base call builds the table)
+  if (p.guard && (rc = vb.acquire())) return rc;
+  const bool four = p.route == ROUTE_FOUR_PER_WAVE, wave = p.route == ROUTE_WAVE_PER_ELEMENT, quad = p.route == ROUTE_QUAD_PER_ELEMENT;
   switch (op) {
-    // Every kernel with a square root or an encoding keeps per-lane state in scratch areas that exist once per device
-    // (round records of the batched inversions, window tables): never more lanes than those areas have (gv), and each
-    // launch queues behind the areas' last user.
     case OP_SQRT:
-      if (n <= tiny4_batch_max(d)) {                          // four elements per wave: power chains on the rows, no scratch
-        hipLaunchKernelGGL(k_sqrt_ratio_zeta_tiny, dim3(tiny4_grid(n)), dim3(64), 0, s, T, (const uint8_t*)in0, (const uint8_t*)in1, n,
+      if (four)
+        hipLaunchKernelGGL(k_sqrt_ratio_zeta_tiny, g, b, 0, s, T, (const uint8_t*)in0, (const uint8_t*)in1, n,
                            (uint8_t*)out0, (uint8_t*)out1, aux);
-        break;
-      }
-      if ((rc = vb.acquire())) return rc;
-      hipLaunchKernelGGL(k_sqrt_ratio_zeta, dim3(gv), dim3(BLOCK), d.chunk_lds[CK_SQRT], s, T, (const uint8_t*)in0, (const uint8_t*)in1, n,
-                         (uint8_t*)out0, (uint8_t*)out1, aux, dcb);
+      else
+        hipLaunchKernelGGL(k_sqrt_ratio_zeta, g, b, d.chunk_lds[CK_SQRT], s, T, (const uint8_t*)in0, (const uint8_t*)in1, n,
+                           (uint8_t*)out0, (uint8_t*)out1, aux, dcb);
       break;
-    case OP_DECOMPRESS: {
-      // from DCB_ASSIST_MIN elements per resident lane: the batched-inverse form (2^19 0.97 against 1.02 ms, 2^20 1.89 / 2.04,
-      // 2^21 3.79 / 4.06, 2^22 7.66 / 8.10); below, the wide grid
-      if (n <= tiny4_batch_max(d)) {
-        hipLaunchKernelGGL(k_decompress_tiny<false>, dim3(tiny4_grid(n)), dim3(64), 0, s, T, (const uint8_t*)in0, n, (uint8_t*)out0, (uint8_t*)out1);
-        break;
-      }
-      const size_t chunked_min = (size_t)d.tuned(D377_TUNE_DECOMPRESS_CHUNKED_MIN,
-                                                 (long long)(d.resident_lanes() * CODEC_CHUNKED_MIN));
-      if (n >= chunked_min) {
-        if ((rc = vb.acquire())) return rc;
-        hipLaunchKernelGGL(k_decompress_chunked, dim3(gv), dim3(BLOCK), d.chunk_lds[CK_DECOMPRESS], s, T, (const uint8_t*)in0, n, (uint64_t*)out0,
+    case OP_DECOMPRESS:
+      if (four)
+        hipLaunchKernelGGL(k_decompress_tiny<false>, g, b, 0, s, T, (const uint8_t*)in0, n, (uint8_t*)out0, (uint8_t*)out1);
+      else if (p.route == ROUTE_LANE_SETS)
+        hipLaunchKernelGGL(k_decompress_chunked, g, b, d.chunk_lds[CK_DECOMPRESS], s, T, (const uint8_t*)in0, n, (uint64_t*)out0,
                            (uint8_t*)out1, dcb);
-        break;
-      }
-      hipLaunchKernelGGL(k_decompress, dim3(g), dim3(BLOCK), 0, s, T, (const uint8_t*)in0, n, (uint64_t*)out0, (uint8_t*)out1);
+      else
+        hipLaunchKernelGGL(k_decompress, g, b, 0, s, T, (const uint8_t*)in0, n, (uint64_t*)out0, (uint8_t*)out1);
       break;
-    }
     case OP_COMPRESS:
-      if (n <= tiny4_batch_max(d)) {
-        hipLaunchKernelGGL(k_compress_tiny, dim3(tiny4_grid(n)), dim3(64), 0, s, T, (const uint64_t*)in0, n, (uint8_t*)out0);
-        break;
-      }
-      if (n >= (size_t)d.tuned(D377_TUNE_DECOMPRESS_CHUNKED_MIN, (long long)(d.resident_lanes() * CODEC_CHUNKED_MIN)) &&   // as OP_DECOMPRESS
-          codec_chunked_ok(d)) {                                                  // codec_chunked.hip
-        if ((rc = vb.acquire())) return rc;
-        if ((rc = codec_chunked_launch(d, s, false, in0, n, out0, nullptr, gv, dcb))) return rc;
-        break;
-      }
-      hipLaunchKernelGGL(k_compress, dim3(g), dim3(BLOCK), 0, s, T, (const uint64_t*)in0, n, (uint8_t*)out0);
+      if (four)
+        hipLaunchKernelGGL(k_compress_tiny, g, b, 0, s, T, (const uint64_t*)in0, n, (uint8_t*)out0);
+      else if (p.route == ROUTE_CODEC_CHUNKED) {                                  // codec_chunked.hip
+        if ((rc = codec_chunked_launch(d, s, false, in0, n, out0, nullptr, p.grid, dcb))) return rc;
+      } else
+        hipLaunchKernelGGL(k_compress, g, b, 0, s, T, (const uint64_t*)in0, n, (uint8_t*)out0);
       break;
     case OP_ROUNDTRIP:
-      if (n <= tiny4_batch_max(d)) {
-        hipLaunchKernelGGL(k_decompress_tiny<true>, dim3(tiny4_grid(n)), dim3(64), 0, s, T, (const uint8_t*)in0, n, (uint8_t*)out0, (uint8_t*)out1);
-        break;
-      }
-      if (n >= (size_t)d.tuned(D377_TUNE_DECOMPRESS_CHUNKED_MIN, (long long)(d.resident_lanes() * CODEC_CHUNKED_MIN)) &&   // as OP_DECOMPRESS
-          codec_chunked_ok(d)) {
-        if ((rc = vb.acquire())) return rc;
-        if ((rc = codec_chunked_launch(d, s, true, in0, n, out0, out1, gv, dcb))) return rc;
-        break;
-      }
-      hipLaunchKernelGGL(k_roundtrip, dim3(g), dim3(BLOCK), 0, s, T, (const uint8_t*)in0, n, (uint8_t*)out0, (uint8_t*)out1);
+      if (four)
+        hipLaunchKernelGGL(k_decompress_tiny<true>, g, b, 0, s, T, (const uint8_t*)in0, n, (uint8_t*)out0, (uint8_t*)out1);
+      else if (p.route == ROUTE_CODEC_CHUNKED) {
+        if ((rc = codec_chunked_launch(d, s, true, in0, n, out0, out1, p.grid, dcb))) return rc;
+      } else
+        hipLaunchKernelGGL(k_roundtrip, g, b, 0, s, T, (const uint8_t*)in0, n, (uint8_t*)out0, (uint8_t*)out1);
       break;
-    case OP_MUL_BASE: {
-      // Wide launch (3 workgroups per CU, 16 elements per inversion) beyond ONE generation of full narrow chunks (DCB_K elements per
-      // resident lane: 2^20 on 256 CUs); up to there the narrow one (2 per CU, 8 per inversion), whose rounds are dealt out
-      // evenly, is as fast or faster (196 608 elements: 166 against 186 us).  Beyond, the narrow launch needs a second
-      // generation of workgroups and the wide one does not: wide / narrow 0.88 at 1.25 x 2^20, 0.95 at 1.5 x, 0.88 at
-      // 1.75 x, 0.96 at 2^21, 0.94-0.95 at 3 x 2^20 and 2^22, warm clocks, alternating (profiles/r05_fb_wide_sweep.txt; the
-      // threshold of rounds 3-4, two generations, was measured on the 18-bit comb before the rounds were dealt out evenly).
-      if ((rc = ensure_comb(d, s))) return rc;                 // (a lazy context's first fixed-base call builds the table)
-      if (n <= tiny_batch_max(d)) {                           // one scalar per wave, lane-spread arithmetic
-        if ((rc = with_fb_bits(d.fb_bits, [&](auto b) -> int {
-               hipLaunchKernelGGL((k_scalar_mul_base_tiny<false, decltype(b)::value>), dim3((unsigned)n), dim3(64), 0, s, d.fbase, (const uint8_t*)in0, n, (uint8_t*)out0);
+    case OP_MUL_BASE:
+      if (wave) {
+        if ((rc = with_fb_bits(d.fb_bits, [&](auto w) -> int {
+               hipLaunchKernelGGL((k_scalar_mul_base_tiny<false, decltype(w)::value>), g, b, 0, s, d.fbase, (const uint8_t*)in0, n, (uint8_t*)out0);
                return D377_OK; }))) return rc;
-        break;
-      }
-      if (n <= small_batch_max(d, false)) {                   // one scalar per quad of lanes
-        if ((rc = with_fb_bits(d.fb_bits, [&](auto b) -> int {
-               hipLaunchKernelGGL((k_scalar_mul_base_small<false, decltype(b)::value>), dim3((unsigned)((n + SMALL_QUADS - 1) / SMALL_QUADS)), dim3(SMALL_THREADS), 0, s,
+      } else if (quad) {
+        if ((rc = with_fb_bits(d.fb_bits, [&](auto w) -> int {
+               hipLaunchKernelGGL((k_scalar_mul_base_small<false, decltype(w)::value>), g, b, 0, s,
                                   d.fbase, (const uint8_t*)in0, n, (uint8_t*)out0);
                return D377_OK; }))) return rc;
-        break;
-      }
-      bool wide = n > d.resident_lanes() * DCB_K * FB_WIDE_GENERATIONS;
-      if (d.is_tuned(D377_TUNE_FB_WIDE)) wide = d.tuned(D377_TUNE_FB_WIDE, 0) != 0;               // developer overrides (A/B)
-      const int fk = (int)d.tuned(D377_TUNE_FB_K, wide ? FB_K : DCB_K);
-      int gb;
-      DcbScratch db;
-      chunks_of(wide ? FB_SETS : WAVES_PER_SIMD, fk, gb, db);
-      // dcb.hpp dcb_progress_priority in the wide launch: one generation only (-1 % at 1.25 x 2^20, -2 % at 2^21); two generations
-      // of waves in step gather their table entries in bursts (+6 to +10 % at 2^22: profiles/r05_ab_progress_priority.txt)
-      if (wide && gb > d.cus * FB_SETS) db.prio = 0;
-      if ((rc = vb.acquire())) return rc;
-      if ((rc = with_fb_bits(d.fb_bits, [&](auto b) -> int {
-             hipLaunchKernelGGL((k_scalar_mul_base<decltype(b)::value>), dim3(gb), dim3(BLOCK), wide ? d.chunk_lds[CK_MUL_BASE] : d.fb_narrow_lds, s, T, d.fbase,
-                                (const uint8_t*)in0, n, (uint8_t*)out0, db);
+      } else if ((rc = with_fb_bits(d.fb_bits, [&](auto w) -> int {
+             hipLaunchKernelGGL((k_scalar_mul_base<decltype(w)::value>), g, b, p.route == ROUTE_FB_WIDE ? d.chunk_lds[CK_MUL_BASE] : d.fb_narrow_lds, s, T, d.fbase,
+                                (const uint8_t*)in0, n, (uint8_t*)out0, dcb);
              return D377_OK; }))) return rc;
       break;
-    }
     case OP_MUL_VAR:
-      if (n <= tiny_batch_max(d)) {                           // one element per wave, lane-spread arithmetic
-        hipLaunchKernelGGL(k_scalar_mul_var_tiny<false>, dim3((unsigned)n), dim3(64), 0, s, T, (const uint8_t*)in0, (const uint8_t*)in1, n,
+      if (wave)
+        hipLaunchKernelGGL(k_scalar_mul_var_tiny<false>, g, b, 0, s, T, (const uint8_t*)in0, (const uint8_t*)in1, n,
                            (uint8_t*)out0, (uint8_t*)out1);
-        break;
-      }
-      if (n <= small_batch_max(d, false)) {                   // one element per quad of lanes, table in LDS: no scratch, no hand-over
-        hipLaunchKernelGGL(k_scalar_mul_var_small<false>, dim3((unsigned)((n + SMALL_QUADS - 1) / SMALL_QUADS)), dim3(SMALL_THREADS), 0, s, T,
+      else if (quad)
+        hipLaunchKernelGGL(k_scalar_mul_var_small<false>, g, b, 0, s, T,
                            (const uint8_t*)in0, (const uint8_t*)in1, n, (uint8_t*)out0, (uint8_t*)out1);
-        break;
-      }
-      if ((rc = vb.acquire())) return rc;
-      hipLaunchKernelGGL(k_scalar_mul_var, dim3(gv), dim3(BLOCK), d.chunk_lds[CK_MUL_VAR], s, T, (const uint8_t*)in0, (const uint8_t*)in1, n,
-                         (uint8_t*)out0, (uint8_t*)out1, d.vb_scratch, (const uint32_t*)d.vb_identity, dcb);
+      else
+        hipLaunchKernelGGL(k_scalar_mul_var, g, b, d.chunk_lds[CK_MUL_VAR], s, T, (const uint8_t*)in0, (const uint8_t*)in1, n,
+                           (uint8_t*)out0, (uint8_t*)out1, d.vb_scratch, (const uint32_t*)d.vb_identity, dcb);
       break;
     case OP_ENCODE:
-      if (n <= tiny4_batch_max(d)) {
-        hipLaunchKernelGGL(k_map_to_curve_tiny, dim3(tiny4_grid(n)), dim3(64), 0, s, T, (const uint8_t*)in0, (const uint8_t*)nullptr, n, (uint8_t*)out0);
-        break;
-      }
-      if ((rc = vb.acquire())) return rc;
-      hipLaunchKernelGGL(k_encode_to_curve, dim3(gv), dim3(BLOCK), d.chunk_lds[CK_ENCODE], s, T, (const uint8_t*)in0, n, (uint8_t*)out0, dcb);
+      if (four)
+        hipLaunchKernelGGL(k_map_to_curve_tiny, g, b, 0, s, T, (const uint8_t*)in0, (const uint8_t*)nullptr, n, (uint8_t*)out0);
+      else
+        hipLaunchKernelGGL(k_encode_to_curve, g, b, d.chunk_lds[CK_ENCODE], s, T, (const uint8_t*)in0, n, (uint8_t*)out0, dcb);
       break;
     case OP_HASH:
-      if (n <= tiny4_batch_max(d) / 2) {                      // two pairs per wave: one pass over the rows for both maps
-        hipLaunchKernelGGL(k_hash_to_curve_tiny2, dim3((unsigned)((n + 1) / 2)), dim3(64), 0, s, T, (const uint8_t*)in0, (const uint8_t*)in1, n, (uint8_t*)out0);
-        break;
-      }
-      if (n <= tiny4_batch_max(d)) {
-        hipLaunchKernelGGL(k_map_to_curve_tiny, dim3(tiny4_grid(n)), dim3(64), 0, s, T, (const uint8_t*)in0, (const uint8_t*)in1, n, (uint8_t*)out0);
-        break;
-      }
-      if ((rc = vb.acquire())) return rc;
-      hipLaunchKernelGGL(k_hash_to_curve, dim3(gv), dim3(BLOCK), d.chunk_lds[CK_HASH], s, T, (const uint8_t*)in0, (const uint8_t*)in1, n,
-                         (uint8_t*)out0, dcb);
+      if (p.route == ROUTE_PAIR_PER_WAVE)
+        hipLaunchKernelGGL(k_hash_to_curve_tiny2, g, b, 0, s, T, (const uint8_t*)in0, (const uint8_t*)in1, n, (uint8_t*)out0);
+      else if (four)
+        hipLaunchKernelGGL(k_map_to_curve_tiny, g, b, 0, s, T, (const uint8_t*)in0, (const uint8_t*)in1, n, (uint8_t*)out0);
+      else
+        hipLaunchKernelGGL(k_hash_to_curve, g, b, d.chunk_lds[CK_HASH], s, T, (const uint8_t*)in0, (const uint8_t*)in1, n,
+                           (uint8_t*)out0, dcb);
       break;
     case OP_ADD:
-      hipLaunchKernelGGL(k_add, dim3(g), dim3(BLOCK), 0, s, (const uint64_t*)in0, (const uint64_t*)in1, n, (uint64_t*)out0, aux);
+      hipLaunchKernelGGL(k_add, g, b, 0, s, (const uint64_t*)in0, (const uint64_t*)in1, n, (uint64_t*)out0, aux);
       break;
     case OP_DOUBLE:
-      hipLaunchKernelGGL(k_double, dim3(g), dim3(BLOCK), 0, s, (const uint64_t*)in0, n, (uint64_t*)out0);
+      hipLaunchKernelGGL(k_double, g, b, 0, s, (const uint64_t*)in0, n, (uint64_t*)out0);
       break;
     case OP_EQ:
-      hipLaunchKernelGGL(k_eq, dim3(g), dim3(BLOCK), 0, s, (const uint64_t*)in0, (const uint64_t*)in1, n, (uint8_t*)out0);
+      hipLaunchKernelGGL(k_eq, g, b, 0, s, (const uint64_t*)in0, (const uint64_t*)in1, n, (uint8_t*)out0);
       break;
     case OP_WIDE48:
     case OP_WIDE64:
-      hipLaunchKernelGGL(k_fq_from_wide, dim3(g), dim3(BLOCK), 0, s, (const uint8_t*)in0, op == OP_WIDE48 ? 48 : 64, n,
+      hipLaunchKernelGGL(k_fq_from_wide, g, b, 0, s, (const uint8_t*)in0, op == OP_WIDE48 ? 48 : 64, n,
                          (uint8_t*)out0);
       break;
     case OP_ENCODE_WIDE48:
     case OP_ENCODE_WIDE64:
-      if ((rc = vb.acquire())) return rc;
-      hipLaunchKernelGGL(k_encode_to_curve_wide, dim3(gv), dim3(BLOCK), d.chunk_lds[CK_ENCODE_WIDE], s, T, (const uint8_t*)in0,
+      hipLaunchKernelGGL(k_encode_to_curve_wide, g, b, d.chunk_lds[CK_ENCODE_WIDE], s, T, (const uint8_t*)in0,
                          op == OP_ENCODE_WIDE48 ? 48 : 64, n, (uint8_t*)out0, dcb);
       break;
-    case OP_AFFINE: {
-      // ~AFFINE_PER_LANE elements per lane so that one inversion serves many, but never fewer lanes than one
-      // wave per SIMD.  Measured (tools/attic/affine_bench.py, 2^20 elements): 0.28 / 0.40 / 0.65 / 1.14 ms at 1 / 2 / 4 / 8
-      // blocks per CU -- every extra lane is an extra 380-operation inversion -- against 2.7 ms for one inversion
-      // per element.  D377_TUNE_AFFINE_BLOCKS_PER_CU is a developer override for that sweep.
-      size_t lanes = (n + AFFINE_PER_LANE - 1) / AFFINE_PER_LANE;
-      const size_t fill = (size_t)d.cus * (size_t)d.tuned(D377_TUNE_AFFINE_BLOCKS_PER_CU, 1) * BLOCK;
-      if (lanes < fill) lanes = fill < n ? fill : n;
-      const int ga = (int)((lanes + BLOCK - 1) / BLOCK);
-      hipLaunchKernelGGL(k_to_affine, dim3(ga), dim3(BLOCK), 0, s, (const uint64_t*)in0, n, (uint64_t*)out0);
+    case OP_AFFINE:
+      hipLaunchKernelGGL(k_to_affine, g, b, 0, s, (const uint64_t*)in0, n, (uint64_t*)out0);
       break;
-    }
     case OP_FQ_BIN:
     case OP_FQ_UN:
       if (op == OP_FQ_UN && aux == D377_FQ_INVERSE)
-        hipLaunchKernelGGL(k_fq_inv, dim3(g), dim3(BLOCK), 0, s, (const uint64_t*)in0, n, (uint64_t*)out0, (uint8_t*)out1);
+        hipLaunchKernelGGL(k_fq_inv, g, b, 0, s, (const uint64_t*)in0, n, (uint64_t*)out0, (uint8_t*)out1);
       else
-        hipLaunchKernelGGL(k_fq_op, dim3(g), dim3(BLOCK), 0, s, aux, (const uint64_t*)in0, (const uint64_t*)in1, n,
+        hipLaunchKernelGGL(k_fq_op, g, b, 0, s, aux, (const uint64_t*)in0, (const uint64_t*)in1, n,
                            (uint64_t*)out0, (uint8_t*)out1);
       break;
     case OP_FQ_CHECKED:
-      hipLaunchKernelGGL(k_fq_from_bytes_checked, dim3(g), dim3(BLOCK), 0, s, (const uint8_t*)in0, n, (uint64_t*)out0, (uint8_t*)out1);
+      hipLaunchKernelGGL(k_fq_from_bytes_checked, g, b, 0, s, (const uint8_t*)in0, n, (uint64_t*)out0, (uint8_t*)out1);
       break;
     case OP_FQ_TO_BYTES:
-      hipLaunchKernelGGL(k_fq_to_bytes, dim3(g), dim3(BLOCK), 0, s, (const uint64_t*)in0, n, (uint8_t*)out0);
+      hipLaunchKernelGGL(k_fq_to_bytes, g, b, 0, s, (const uint64_t*)in0, n, (uint8_t*)out0);
       break;
     case OP_FR_MOD:
-      hipLaunchKernelGGL(k_fr_bytes, dim3(g), dim3(BLOCK), 0, s, (const uint8_t*)in0, n, (uint8_t*)out0, (uint8_t*)nullptr);
+      hipLaunchKernelGGL(k_fr_bytes, g, b, 0, s, (const uint8_t*)in0, n, (uint8_t*)out0, (uint8_t*)nullptr);
       break;
     case OP_FR_CHECKED:
-      hipLaunchKernelGGL(k_fr_bytes, dim3(g), dim3(BLOCK), 0, s, (const uint8_t*)in0, n, (uint8_t*)out0, (uint8_t*)out1);
+      hipLaunchKernelGGL(k_fr_bytes, g, b, 0, s, (const uint8_t*)in0, n, (uint8_t*)out0, (uint8_t*)out1);
       break;
     case OP_NEG:
-      hipLaunchKernelGGL(k_neg, dim3(g), dim3(BLOCK), 0, s, (const uint64_t*)in0, n, (uint64_t*)out0);
+      hipLaunchKernelGGL(k_neg, g, b, 0, s, (const uint64_t*)in0, n, (uint64_t*)out0);
       break;
-    case OP_MUL_VAR_EL: {
-      if (n <= tiny_batch_max(d)) {
-        hipLaunchKernelGGL(k_scalar_mul_var_tiny<true>, dim3((unsigned)n), dim3(64), 0, s, T, (const uint8_t*)in0, (const uint8_t*)in1, n,
+    case OP_MUL_VAR_EL:
+      if (wave)
+        hipLaunchKernelGGL(k_scalar_mul_var_tiny<true>, g, b, 0, s, T, (const uint8_t*)in0, (const uint8_t*)in1, n,
                            (uint8_t*)out0, (uint8_t*)nullptr);
-        break;
-      }
-      if (n <= small_batch_max(d, true)) {
-        hipLaunchKernelGGL(k_scalar_mul_var_small<true>, dim3((unsigned)((n + SMALL_QUADS - 1) / SMALL_QUADS)), dim3(SMALL_THREADS), 0, s, T,
+      else if (quad)
+        hipLaunchKernelGGL(k_scalar_mul_var_small<true>, g, b, 0, s, T,
                            (const uint8_t*)in0, (const uint8_t*)in1, n, (uint8_t*)out0, (uint8_t*)nullptr);
-        break;
-      }
-      // no inversions here, so nothing argues for long chunks: one or two elements per lane keep the grid oversubscribed
-      // at every batch size
-      // (2^20 elements: 7.33e7/s with 8 per lane, 7.44 with 4, 7.59 with 2, 7.54 with 1)
-      DcbScratch dv = dcb;
-      dv.extra = 0;                                          // this kernel walks uniform chunks
-      dv.per_lane = n > d.resident_lanes() ? 2 : 1;
-      size_t nch = (n + (size_t)dv.per_lane * BLOCK - 1) / ((size_t)dv.per_lane * BLOCK);
-      if (nch > (size_t)d.cus * 64) nch = (size_t)d.cus * 64;
-      // `dcb` carries the priority rule of ITS deal (chunks of up to 16 per lane); this launch has its own shape -- 8 192 chunks
-      // in 16 generations at 2^22 -- and the rule is about generations: priorities in launches of one or two of them
-      dv.prio = nch <= 2 * (size_t)d.cus * WAVES_PER_SIMD ? 1 : 0;
-      if ((rc = vb.acquire())) return rc;
-      hipLaunchKernelGGL(k_scalar_mul_var_el, dim3((int)nch), dim3(BLOCK), d.chunk_lds[CK_MUL_VAR_EL], s, (const uint64_t*)in0, (const uint8_t*)in1, n,
-                         (uint64_t*)out0, d.vb_scratch, (const uint32_t*)d.vb_identity, dv);
+      else
+        hipLaunchKernelGGL(k_scalar_mul_var_el, g, b, d.chunk_lds[CK_MUL_VAR_EL], s, (const uint64_t*)in0, (const uint8_t*)in1, n,
+                           (uint64_t*)out0, d.vb_scratch, (const uint32_t*)d.vb_identity, dcb);
       break;
-    }
     case OP_MUL_BASE_EL:
-      if ((rc = ensure_comb(d, s))) return rc;
-      if ((rc = with_fb_bits(d.fb_bits, [&](auto b) -> int {
-             constexpr int BITS = decltype(b)::value;
-             if (n <= tiny_batch_max(d))
-               hipLaunchKernelGGL((k_scalar_mul_base_tiny<true, BITS>), dim3((unsigned)n), dim3(64), 0, s, d.fbase, (const uint8_t*)in0, n, (uint8_t*)out0);
-             else if (n <= small_batch_max(d, true))
-               hipLaunchKernelGGL((k_scalar_mul_base_small<true, BITS>), dim3((unsigned)((n + SMALL_QUADS - 1) / SMALL_QUADS)), dim3(SMALL_THREADS), 0, s, d.fbase,
-                                  (const uint8_t*)in0, n, (uint8_t*)out0);
+      if ((rc = with_fb_bits(d.fb_bits, [&](auto w) -> int {
+             constexpr int BITS = decltype(w)::value;
+             if (wave)
+               hipLaunchKernelGGL((k_scalar_mul_base_tiny<true, BITS>), g, b, 0, s, d.fbase, (const uint8_t*)in0, n, (uint8_t*)out0);
+             else if (quad)
+               hipLaunchKernelGGL((k_scalar_mul_base_small<true, BITS>), g, b, 0, s, d.fbase, (const uint8_t*)in0, n, (uint8_t*)out0);
              else
-               hipLaunchKernelGGL((k_scalar_mul_base_el<BITS>), dim3(g), dim3(BLOCK), 0, s, d.fbase, (const uint8_t*)in0, n, (uint64_t*)out0);
+               hipLaunchKernelGGL((k_scalar_mul_base_el<BITS>), g, b, 0, s, d.fbase, (const uint8_t*)in0, n, (uint64_t*)out0);
              return D377_OK; }))) return rc;
       break;
     case OP_COMPRESS_FIELD:
-      hipLaunchKernelGGL(k_compress_to_field, dim3(g), dim3(BLOCK), 0, s, T, (const uint64_t*)in0, n, (uint64_t*)out0);
+      hipLaunchKernelGGL(k_compress_to_field, g, b, 0, s, T, (const uint64_t*)in0, n, (uint64_t*)out0);
       break;
     case OP_ENCODE_EL:
     case OP_HASH_EL:
-      if ((rc = vb.acquire())) return rc;
-      hipLaunchKernelGGL(k_map_to_element, dim3(gv), dim3(BLOCK), d.chunk_lds[CK_MAP_EL], s, T, (const uint8_t*)in0,
+      hipLaunchKernelGGL(k_map_to_element, g, b, d.chunk_lds[CK_MAP_EL], s, T, (const uint8_t*)in0,
                          op == OP_HASH_EL ? (const uint8_t*)in1 : (const uint8_t*)nullptr, n, (uint64_t*)out0, dcb);
       break;
     case OP_FR_BIN:
     case OP_FR_UN:
-      hipLaunchKernelGGL(k_fr_op, dim3(g), dim3(BLOCK), 0, s, aux, (const uint8_t*)in0, (const uint8_t*)in1, n, (uint8_t*)out0,
+      hipLaunchKernelGGL(k_fr_op, g, b, 0, s, aux, (const uint8_t*)in0, (const uint8_t*)in1, n, (uint8_t*)out0,
                          (uint8_t*)out1);
       break;
     case OP_FR_WIDE48:
     case OP_FR_WIDE64:
-      hipLaunchKernelGGL(k_fr_from_wide, dim3(g), dim3(BLOCK), 0, s, (const uint8_t*)in0, op == OP_FR_WIDE48 ? 48 : 64, n,
+      hipLaunchKernelGGL(k_fr_from_wide, g, b, 0, s, (const uint8_t*)in0, op == OP_FR_WIDE48 ? 48 : 64, n,
                          (uint8_t*)out0);
       break;
     case OP_IS_IDENTITY:
-      hipLaunchKernelGGL(k_is_identity, dim3(g), dim3(BLOCK), 0, s, (const uint64_t*)in0, n, (uint8_t*)out0);
+      hipLaunchKernelGGL(k_is_identity, g, b, 0, s, (const uint64_t*)in0, n, (uint8_t*)out0);
       break;
   }
   HIP_TRY(hipGetLastError());
@@ -1898,11 +1774,7 @@ OpShape shape_of(Op op) {
   return {0, 0, 0, 0};
 }
 
-// Large batches are pipelined in chunks of 2^18 records: while chunk k runs on the compute stream,
-// chunk k+1's inputs are copied in and chunk k-1's outputs are copied out on the copy stream
-// (double-buffered staging), so PCIe time hides under the kernels.
-constexpr size_t PIPE_CHUNK = (size_t)1 << 18;
-
+// Large batches are pipelined in chunks of PIPE_CHUNK records (launch_plan.hpp: host_path_pipelined)
 int run_one_pipelined(DeviceState& d, Op op, int aux, const OpShape& sh, const void* in0, const void* in1, size_t n,
                       void* out0, void* out1) {
   int rc = D377_OK;
@@ -1953,33 +1825,27 @@ int run_one_pipelined(DeviceState& d, Op op, int aux, const OpShape& sh, const v
   return rc;
 }
 
-// one device, one contiguous slice of a host batch: copies in, kernel, copies out, synchronised
+// one device, one contiguous slice of a host batch: copies in, kernel, copies out, synchronised (batch_host.hpp: device_slice)
 int run_one(DeviceState& d, Op op, int aux, const OpShape& sh, const void* in0, const void* in1, size_t n, void* out0,
             void* out1) {
   if (n == 0) return D377_OK;
-  HIP_TRY(hipSetDevice(d.id));
-  if (n >= 2 * PIPE_CHUNK) return run_one_pipelined(d, op, aux, sh, in0, in1, n, out0, out1);
-  int rc = D377_OK;
-  SyncOnError guard{&rc, d.id, d.stream, nullptr};
-  auto body = [&]() -> int {
+  if (host_path_pipelined(n)) {
+    HIP_TRY(hipSetDevice(d.id));
+    return run_one_pipelined(d, op, aux, sh, in0, in1, n, out0, out1);
+  }
+  return device_slice(d, [&]() -> int {
     int r;
     if ((r = ensure(d, 0, n * sh.in0))) return r;
     if (sh.in1 && (r = ensure(d, 1, n * sh.in1))) return r;
     if ((r = ensure(d, 2, n * sh.out0))) return r;
     if (sh.out1 && (r = ensure(d, 3, n * sh.out1))) return r;
-    StarveCheck starve{d, d.stream};
-    if ((r = starve.before())) return r;
     HIP_TRY(hipMemcpyAsync(d.buf[0], in0, n * sh.in0, hipMemcpyHostToDevice, d.stream));
     if (sh.in1) HIP_TRY(hipMemcpyAsync(d.buf[1], in1, n * sh.in1, hipMemcpyHostToDevice, d.stream));
     if ((r = launch(d, d.stream, op, aux, d.buf[0], d.buf[1], n, d.buf[2], d.buf[3]))) return r;
     HIP_TRY(hipMemcpyAsync(out0, d.buf[2], n * sh.out0, hipMemcpyDeviceToHost, d.stream));
     if (sh.out1) HIP_TRY(hipMemcpyAsync(out1, d.buf[3], n * sh.out1, hipMemcpyDeviceToHost, d.stream));
-    if ((r = starve.after())) return r;
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    return starve.verdict();
-  };
-  rc = body();
-  return rc;
+    return D377_OK;
+  });
 }
 
 // host-pointer path: contiguous slices over the context's devices (host_state.hpp: slice_over_devices)

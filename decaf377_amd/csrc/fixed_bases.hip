@@ -276,8 +276,7 @@ int fixed_msm_long_launch(DeviceState& d, hipStream_t s, const FixedBases& fb, c
   uint64_t* partials = nullptr;
   if ((rc = long_sums_partials(d, s, n, plan.g, &partials))) return rc;
   if ((rc = vb.acquire())) return rc;
-  size_t grid = (n * plan.g + BLOCK - 1) / BLOCK;
-  if (grid > (size_t)d.cus * 8) grid = (size_t)d.cus * 8;    // (as the fold's)
+  const int grid = fold_grid(d, n * plan.g);
   const SqrtTables T = d.tables();
   if ((rc = with_width(fb.bits, WIDTH_REFUSAL, [&](auto b) -> int {
          hipLaunchKernelGGL(k_fixed_msm_seg<decltype(b)::value>, dim3((unsigned)grid), dim3(BLOCK), 0, s, T, tab, scalars, plan, n, partials);
@@ -387,9 +386,7 @@ int index_verdict_launch(DeviceState& d, hipStream_t s, const int* base_index, s
   hipLaunchKernelGGL(k_index_verdict_init, dim3(1), dim3(64), 0, s, verdict);
   HIP_TRY(hipGetLastError());
   if (count == 0) return D377_OK;
-  size_t grid = (count + BLOCK - 1) / BLOCK;
-  if (grid > (size_t)d.cus * 8) grid = (size_t)d.cus * 8;    // (as the fold's)
-  hipLaunchKernelGGL(k_index_verdict, dim3((unsigned)grid), dim3(BLOCK), 0, s, base_index, count, m, verdict);
+  hipLaunchKernelGGL(k_index_verdict, dim3((unsigned)fold_grid(d, count)), dim3(BLOCK), 0, s, base_index, count, m, verdict);
   HIP_TRY(hipGetLastError());
   return D377_OK;
 }

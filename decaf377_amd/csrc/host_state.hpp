@@ -13,6 +13,7 @@
 #include "../../include/decaf377_amd.h"
 #include "curve.hpp"
 #include "device_util.hpp"
+#include "launch_plan.hpp"
 
 extern thread_local char d377_g_err[512];
 
@@ -86,19 +87,10 @@ struct MsmWorkspace {
 // chunk_sets[k] workgroups of kernel k may be resident per CU -- that is how many lane sets it may claim; d377_ctx_create checks
 // each with hipOccupancyMaxActiveBlocksPerMultiprocessor and pads the launch's LDS allocation for a kernel whose
 // registers and own LDS would let more in (chunk_lds, bytes of dynamic LDS per launch).
-// Developer tuning (d377_ctx_set_tuning): one value per D377_TUNE_* key, D377_TUNE_DEFAULT = the built-in rule.  Lives in
-// the context, written and read under d377_ctx::mu (every launch path holds it); nothing on a call path reads the
-// process environment.
-struct Tuning {
-  int64_t v[D377_TUNE_COUNT];
-  Tuning() { for (int k = 0; k < D377_TUNE_COUNT; ++k) v[k] = D377_TUNE_DEFAULT; }
-};
-
 enum ChunkKernel { CK_SQRT, CK_ENCODE, CK_HASH, CK_MUL_VAR, CK_MUL_BASE, CK_MUL_VAR_EL, CK_MAP_EL, CK_ENCODE_WIDE, CK_DECOMPRESS, CK_COUNT };
 
-struct DeviceState {
+struct DeviceState : PlanDev {               // (launch_plan.hpp: the CU count and the context's overrides, as the launch rules read them)
   int id = -1;
-  int cus = 0;
   int chunk_lds[CK_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
   int chunk_blocks[CK_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};     // resident workgroups per CU with that padding (occupancy query)
   int chunk_sets[CK_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};       // lane sets per CU the kernel may claim = the residency it is launched for
@@ -152,46 +144,8 @@ struct DeviceState {
   size_t shard_cap[4] = {0, 0, 0, 0};
   hipEvent_t ev_shard = nullptr;
   MsmWorkspace msm;
-  const Tuning* tune = nullptr;          // the owning context's overrides
-  // the override for `key`, or `dflt` when the built-in rule is in force
-  long long tuned(int key, long long dflt) const { return (tune && tune->v[key] >= 0) ? tune->v[key] : dflt; }
-  bool is_tuned(int key) const { return tune && tune->v[key] >= 0; }
-  // lanes the chunked kernels keep resident (WAVES_PER_SIMD workgroups of BLOCK lanes per CU): the unit the batch-size
-  // thresholds of the launch rules are written in, so that they follow the device's CU count
-  size_t resident_lanes() const { return (size_t)cus * WAVES_PER_SIMD * BLOCK; }
   SqrtTables tables() const { return SqrtTables{gtab, s_lookup, inv_fail}; }
 };
-
-// Workgroups of BLOCK lanes for n elements: >> 256 workgroups when the batch allows it; capped so huge batches grid-stride
-inline int grid_of(const DeviceState& d, size_t n) {
-  size_t blocks = (n + BLOCK - 1) / BLOCK;
-  size_t cap = (size_t)d.cus * 32;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
-
-// How a chunked kernel's rounds (of BLOCK elements) are dealt out to its workgroups.  `places` workgroups are resident at a
-// time and a chunk holds at most kmax rounds (elements per lane).  Up to one round per place: a workgroup per round.
-// Otherwise G = the fewest generations of resident workgroups that can hold the rounds: exactly G x places chunks, the rounds
-// dealt out evenly, the first `extra` chunks one round longer (DcbScratch::extra) -- every generation is full and there is
-// no last generation of a few stragglers.  (Chunks of kmax left 5 x 2^18 elements with 128 of them: sqrt_ratio_zeta 2.54 ms
-// against 2.13 dealt evenly, variable base 24.1 against 19.4: profiles/r05_chunk_between_generations.txt.)  Whole multiples
-// of places x kmax rounds -- 2^20, 2^21, 2^22 elements on 256 CUs -- come out as chunks of kmax, as before.  Beyond `cap`
-// chunks the workgroups walk several chunks of kmax.
-struct ChunkDeal { size_t per_lane, extra, nchunks; };
-inline ChunkDeal deal_chunks(size_t rounds, size_t places, size_t kmax, size_t cap) {
-  ChunkDeal c{1, 0, rounds};
-  if (rounds <= places) return c;
-  const size_t gens = (rounds + places * kmax - 1) / (places * kmax);
-  if (gens * places <= cap) {
-    c.nchunks = gens * places; c.per_lane = rounds / c.nchunks; c.extra = rounds % c.nchunks;
-  } else {
-    c.per_lane = kmax; c.nchunks = (rounds + kmax - 1) / kmax;
-    if (c.nchunks > cap) c.nchunks = cap;
-  }
-  return c;
-}
 
 inline int grow(uint8_t*& p, size_t& cap, size_t bytes, size_t slack) {
   if (bytes <= cap) return D377_OK;
@@ -252,12 +206,6 @@ struct StarveCheck {
     return D377_ERR_STARVED;
   }
 };
-
-// op codes of the generic launcher in d377.hip (shared with the sharded path)
-enum Op { OP_SQRT, OP_DECOMPRESS, OP_COMPRESS, OP_ROUNDTRIP, OP_MUL_BASE, OP_MUL_VAR, OP_ENCODE, OP_HASH, OP_ADD, OP_DOUBLE,
-          OP_EQ, OP_WIDE48, OP_WIDE64, OP_ENCODE_WIDE48, OP_ENCODE_WIDE64, OP_AFFINE, OP_NEG, OP_IS_IDENTITY, OP_FQ_BIN,
-          OP_FQ_UN, OP_FQ_CHECKED, OP_FQ_TO_BYTES, OP_FR_MOD, OP_FR_CHECKED, OP_MUL_VAR_EL, OP_MUL_BASE_EL, OP_COMPRESS_FIELD,
-          OP_ENCODE_EL, OP_HASH_EL, OP_FR_BIN, OP_FR_UN, OP_FR_WIDE48, OP_FR_WIDE64 };
 
 // D377_DEBUG_DEVICE_DELAY_MS (tests only): every per-device worker of a multi-device host call sleeps this
 // long before it touches its device, which makes "the devices work concurrently" observable on a box

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "curve.hpp"
+#include "launch_plan.hpp"
 
 namespace d377 {
 
@@ -45,7 +46,7 @@ D377_HD uint32_t span_partials(uint32_t o, uint32_t size, uint32_t L) { return s
 
 // ---- the bucket method's constants (the kernels of msm.hip read them here) ------------------------------------------------
 // Sizes of device_util.hpp and row_ops.hpp (device-only headers) that the plan needs; msm.hip pins them with static_asserts.
-constexpr int PLAN_BLOCK = 256;         // BLOCK
+//                                         (PLAN_BLOCK, BLOCK: launch_plan.hpp)
 constexpr int PLAN_AP_WORDS = 32;       // AP_WORDS: the affine cached point record
 constexpr int PLAN_RQ_WORDS = 64;       // row::RQ_WORDS: one record of the Horner chain in the lane-spread form
 constexpr int PT_WORDS = 48;            // one cached or extended point record: 4 * SLOT words, 192 B
