@@ -25,9 +25,17 @@
  * return as soon as the work is enqueued, and calls on DIFFERENT streams may be in flight at the
  * same time: the per-device scratch areas some kernels use (the variable-base window tables, the records of
  * the batched inversions behind scalar_mul_var / scalar_mul_base / encode_to_curve[_wide] / hash_to_curve /
- * sqrt_ratio_zeta, the MSM workspace) are handed from one launch to the next by events on the device, so such launches queue
+ * sqrt_ratio_zeta, the Straus table scratch of the batched small, mixed, long and long-indexed sums, the partial-sums area
+ * of the long, the long-indexed and the segmented fixed-base sums, the MSM workspace) are handed from one launch to the next
+ * by events on the device, so such launches queue
  * up behind each other instead of racing -- results are the same as if the calls had been made one
  * after another; only their overlap is lost.  Kernels that use no scratch overlap freely.
+ * There are two hand-overs per device.  One covers the lane-set areas, the table scratch and the partial-sums area: every
+ * batched sum (d377_batch_msm_small*, d377_batch_msm_mixed*, d377_batch_long_msm*, d377_batch_fixed_*msm*) queues on it,
+ * whatever its shape.  The other covers the MSM workspace, which d377_msm* and the bucket sums (d377_batch_bucket_msm*)
+ * share: the two queue behind each other.  A call that outgrows an area waits on the host for the area's last user before
+ * it frees it, d377_fixed_bases_destroy waits for the last launch on the combs, and a host-pointer call (the context's
+ * private stream) queues behind `_dev` / `_resident` calls in flight like any other stream.
  * `_dev` calls only enqueue kernels (no host synchronisation, no allocation once the workspaces have grown
  * to the batch size), so a sequence of them can be captured into a hipGraph and replayed.  A capturing stream takes
  * no part in the event hand-over (the graph keeps its own order), so for a REPLAY that overlaps other calls on the same

@@ -1,5 +1,6 @@
 """What the tests of the batched sums share, one copy each: planted scalars and bases, the oracle's byte-table fold over fixed
-bases (Fold), device copies and resident calls on a side stream (Side), and the build-and-run of a C++ mirror program."""
+bases (Fold), device copies and resident calls on a side stream (Side), the gate and the stream control of the two-stream
+cases (Gate, pick_independent_stream), and the build-and-run of a C++ mirror program."""
 import ctypes
 import os
 import subprocess
@@ -193,11 +194,13 @@ def mixed_case(oracle, v, t, m, n, seed=0):
 
 
 class Side:
-    """Device copies of host arrays and the resident calls on ONE side stream; host() synchronises that stream alone."""
+    """Device copies of host arrays and the resident calls on ONE side stream; host() synchronises that stream alone.
+    stream2: an optional second stream for the two-stream cases (pick_independent_stream); nothing here uses it unasked."""
 
-    def __init__(self, torch, ctx):
+    def __init__(self, torch, ctx, stream2=None):
         self.torch, self.ctx, self.lib = torch, ctx, ctx._lib
         self.stream = torch.cuda.Stream(device="cuda:0")
+        self.stream2 = stream2
 
     def dev(self, a):
         a = np.ascontiguousarray(a)
@@ -225,6 +228,81 @@ class Side:
         self.stream.synchronize()
         a = t.cpu().numpy()
         return a.view(np.uint64) if a.dtype == np.int64 else a
+
+
+class Gate:
+    """A stretch of plain torch kernels (y = x @ w, the two buffers swapping) that keeps a stream busy for at least min_ms:
+    whatever is enqueued behind it on that stream cannot start before it ends, however fast the host is.  The loop count is
+    sized once: a short probe gives the time per kernel, the sized loop is then timed once with torch events (`measured_ms`,
+    at least min_ms or the constructor fails).  start() makes no call of the library under test and no tensor."""
+
+    def __init__(self, torch, min_ms=200.0, size=4096, aim=1.5):
+        self.torch, self.min_ms = torch, min_ms
+        self.stream = torch.cuda.Stream(device="cuda:0")         # the sizing runs here, not on the streams of the cases
+        g = torch.Generator(device="cuda:0").manual_seed(1)
+        self.x = torch.randn((size, size), device="cuda:0", generator=g)
+        self.y = torch.empty_like(self.x)
+        self.w = torch.randn((size, size), device="cuda:0", generator=g) / size ** 0.5   # (keeps the products' size steady)
+        torch.cuda.synchronize()
+        self.count = 2
+        self._timed()                                            # warm-up: the BLAS library's own set-up
+        probe = 16
+        self.count = probe
+        per = self._timed() / probe
+        self.count = max(probe, int(aim * min_ms / per) + 1)
+        self.measured_ms = self._timed()                         # the one timing of the sized loop
+        assert self.measured_ms >= min_ms, "the gate takes %.1f ms at %d kernels, under %.0f" % (self.measured_ms, self.count, min_ms)
+
+    def _timed(self):
+        t0, t1 = self.torch.cuda.Event(enable_timing=True), self.torch.cuda.Event(enable_timing=True)
+        t0.record(self.stream)
+        end = self.start(self.stream)
+        t1.record(self.stream)
+        end.synchronize()
+        t1.synchronize()
+        return t0.elapsed_time(t1)
+
+    def start(self, stream):
+        """Enqueues the gate on `stream` -> the event recorded behind its last kernel (query() is false while it runs)."""
+        torch = self.torch
+        a, b = self.x, self.y
+        with torch.cuda.stream(stream):
+            for _ in range(self.count):
+                torch.mm(a, self.w, out=b)
+                a, b = b, a
+        end = torch.cuda.Event()
+        end.record(stream)
+        return end
+
+
+def runs_beside(torch, gate, s1, work):
+    """Does `work()` -- which enqueues something and waits for it on the host -- come back while a gate is still running on
+    s1?  True: what it ran on shares no queue with s1.  (False costs the whole gate: the wait ended with it.)"""
+    end = gate.start(s1)
+    work()
+    beside = not end.query()
+    s1.synchronize()
+    return beside
+
+
+def pick_independent_stream(torch, gate, s1, candidates=8):
+    """The control of the two-stream cases: HIP maps streams onto a few hardware queues, and two streams on one queue run in
+    order with or without a guard.  Tries up to `candidates` fresh streams: with a gate running on s1, one trivial torch op on
+    the candidate and a synchronize() of it; the candidate is independent of s1 if the gate is still running afterwards.
+    -> (stream or None, the candidate's number or None)."""
+    probe = torch.zeros(64, device="cuda:0")
+    torch.cuda.synchronize()
+    for c in range(candidates):
+        s = torch.cuda.Stream(device="cuda:0")
+
+        def work():
+            with torch.cuda.stream(s):
+                probe.add_(1)
+            s.synchronize()
+
+        if runs_beside(torch, gate, s1, work):
+            return s, c
+    return None, None
 
 
 def build_and_run_cpp(name, marker, hip_headers=False):
