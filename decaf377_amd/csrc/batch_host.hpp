@@ -43,21 +43,10 @@ inline int straus_scratch_reserve(DeviceState& d, hipStream_t s, size_t terms, c
                                   uint32_t** tab, uint32_t** dig) {
   const size_t tab_words = d.resident_lanes() * terms * VB_ENTRIES * BM_ENTRY_WORDS;
   const size_t need = (tab_words + d.resident_lanes() * BM_WINDOWS) * sizeof(uint32_t);
-  if (need > d.bm_cap) {
-    if (ScratchGuard::capturing(s)) return fail(D377_ERR_ARG, "%s", in_capture);
-    int rc;
-    if ((rc = d.vb_guard.drain())) return rc;               // a launch on another stream may still be using the old area
-    uint32_t* old = d.bm_scratch;
-    d.bm_scratch = nullptr; d.bm_cap = 0;
-    if ((rc = retire_scratch(d, old))) return rc;              // (kept where a captured graph may still point into it)
-    if (hipMalloc(&d.bm_scratch, need) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(D377_ERR_HIP, "%s", no_memory);
-    }
-    d.bm_cap = need;
-  }
-  *tab = d.bm_scratch;
-  *dig = d.bm_scratch + tab_words;
+  int rc;
+  if ((rc = d.bm_scratch.reserve(d.vb_guard, s, need, SLACK_TABLE_SCRATCH, in_capture, no_memory))) return rc;
+  *tab = d.bm_scratch.as<uint32_t>();
+  *dig = *tab + tab_words;
   return D377_OK;
 }
 

@@ -139,23 +139,6 @@ int fail_size(int code, const char* fmt, size_t a) {
 // records the area must hold for n sums of g partial sums: the partial sums, then the two halves the fold levels alternate between
 size_t partial_records(size_t n, size_t g) { return n * g + 2 * n * fold_out(g); }
 
-// the per-device partials area: grown on demand, never shrunk.  The caller holds ctx->mu and the lane-set guard's scope.
-int ensure_partials(DeviceState& d, size_t bytes) {
-  if (bytes <= d.bml_cap) return D377_OK;
-  int rc;
-  if ((rc = d.vb_guard.drain())) return rc;                  // (every user of the area queues behind the guard)
-  uint8_t* old = d.bml_partials;
-  d.bml_partials = nullptr; d.bml_cap = 0;
-  if ((rc = retire_scratch(d, old))) return rc;              // (kept where a captured graph may still point into it)
-  const size_t want = bytes + bytes / 4 + 4096;
-  if (hipMalloc(&d.bml_partials, want) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail_size(D377_ERR_HIP, "batch_msm_long: hipMalloc of the partial sums' area failed (%zu bytes: 128 bytes per group of up to 8 terms)", want);
-  }
-  d.bml_cap = want;
-  return D377_OK;
-}
-
 }  // namespace
 
 // ---- what both this unit's chains and fixed_bases.hip's segments end in (msm_long_fold.hpp) ----------------------------------
@@ -163,16 +146,16 @@ namespace d377 {
 
 int long_sums_partials(DeviceState& d, hipStream_t s, size_t n, size_t g, uint64_t** partials) {
   *partials = nullptr;
-  if (partial_records(n, g) * 128 > d.bml_cap && ScratchGuard::capturing(s))
-    return fail(D377_ERR_ARG, "%s", "batch_msm_long: the partial sums' area must grow, which cannot happen inside a stream capture");
   int rc;
-  if ((rc = ensure_partials(d, partial_records(n, g) * 128))) return rc;
-  *partials = reinterpret_cast<uint64_t*>(d.bml_partials);
+  if ((rc = d.bml_partials.reserve(d.vb_guard, s, partial_records(n, g) * 128, SLACK_PARTIALS,
+         "batch_msm_long: the partial sums' area must grow, which cannot happen inside a stream capture",
+         "batch_msm_long: hipMalloc of the partial sums' area failed (%zu bytes: 128 bytes per group of up to 8 terms)"))) return rc;
+  *partials = d.bml_partials.as<uint64_t>();
   return D377_OK;
 }
 
 int long_sums_fold_compress(DeviceState& d, hipStream_t s, size_t n, size_t g, uint8_t* out32, uint64_t* xyzt_out) {
-  uint64_t* partials = reinterpret_cast<uint64_t*>(d.bml_partials);
+  uint64_t* partials = d.bml_partials.as<uint64_t>();
   const size_t np = n * g;
   uint64_t* half[2] = {partials + np * 16, partials + (np + n * fold_out(g)) * 16};
 

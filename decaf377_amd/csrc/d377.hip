@@ -1466,7 +1466,7 @@ int init_device(DeviceState& d) {
   }
   HIP_TRY(hipEventCreateWithFlags(&d.ev_shard, hipEventDisableTiming));
   int rc;
-  if ((rc = d.vb_guard.init()) || (rc = d.msm.guard.init())) return rc;
+  if ((rc = d.vb_guard.init()) || (rc = d.msm_guard.init())) return rc;
   HIP_TRY(hipMalloc(&d.gtab, (size_t)6 * 256 * GT_STRIDE * sizeof(uint32_t)));
   HIP_TRY(hipMalloc(&d.s_lookup, (size_t)1 << S_HASH_BITS));
   HIP_TRY(hipMalloc(&d.inv_fail, sizeof(uint32_t)));
@@ -1515,8 +1515,8 @@ void free_device(DeviceState& d) {
   if (d.stream) (void)hipStreamSynchronize(d.stream);
   if (d.copy_stream) (void)hipStreamSynchronize(d.copy_stream);
   (void)d.vb_guard.drain();
-  (void)d.msm.guard.drain();
-  (void)hipFree(d.gtab); (void)hipFree(d.s_lookup); (void)hipFree(d.fbase); (void)hipFree(d.fb_bases); (void)hipFree(d.bm_scratch); (void)hipFree(d.bml_partials); (void)hipFree(d.vb_scratch); (void)hipFree(d.vb_identity); (void)hipFree(d.dcb_scratch); (void)hipFree(d.slot_pool); (void)hipFree(d.pool_health); (void)hipFree(d.inv_fail);
+  (void)d.msm_guard.drain();
+  (void)hipFree(d.gtab); (void)hipFree(d.s_lookup); (void)hipFree(d.fbase); (void)hipFree(d.fb_bases); (void)hipFree(d.vb_scratch); (void)hipFree(d.vb_identity); (void)hipFree(d.dcb_scratch); (void)hipFree(d.slot_pool); (void)hipFree(d.pool_health); (void)hipFree(d.inv_fail);
   if (d.starve_host) (void)hipHostFree(d.starve_host);
   d.starve_host = nullptr;
   if (d.pool_host) (void)hipHostFree(d.pool_host);
@@ -1528,15 +1528,11 @@ void free_device(DeviceState& d) {
     if (d.ev_done[i]) (void)hipEventDestroy(d.ev_done[i]);
   }
   if (d.ev_shard) (void)hipEventDestroy(d.ev_shard);
-  d.vb_guard.destroy();
-  d.msm.guard.destroy();
+  d.bm_scratch.release(); d.bml_partials.release(); d.msm_ws.release();
+  d.vb_guard.destroy();                    // (with the blocks retired under it)
+  d.msm_guard.destroy();
   if (d.copy_stream) (void)hipStreamDestroy(d.copy_stream);
   if (d.ctl_stream) (void)hipStreamDestroy(d.ctl_stream);
-  (void)hipFree(d.msm.mem);
-  for (uint8_t* r : d.msm.retired) (void)hipFree(r);
-  d.msm.retired.clear();
-  for (void* r : d.vb_retired) (void)hipFree(r);
-  d.vb_retired.clear();
   if (d.stream) (void)hipStreamDestroy(d.stream);
 }
 
@@ -2143,7 +2139,7 @@ int d377_ctx_starved_counter_dev(d377_ctx* ctx, int dev, const uint32_t** counte
 static bool device_busy(DeviceState& d) {
   if (hipStreamQuery(d.stream) == hipErrorNotReady) return true;
   if (d.vb_guard.used && hipEventQuery(d.vb_guard.ev) == hipErrorNotReady) return true;
-  if (d.msm.guard.used && hipEventQuery(d.msm.guard.ev) == hipErrorNotReady) return true;
+  if (d.msm_guard.used && hipEventQuery(d.msm_guard.ev) == hipErrorNotReady) return true;
   (void)hipGetLastError();
   return false;
 }

@@ -14,74 +14,9 @@
 #include "curve.hpp"
 #include "device_util.hpp"
 #include "launch_plan.hpp"
-
-extern thread_local char d377_g_err[512];
+#include "scratch_area.hpp"
 
 namespace d377 {
-
-inline int fail(int code, const char* fmt, const char* detail) {
-  snprintf(d377_g_err, sizeof d377_g_err, fmt, detail);
-  return code;
-}
-#define HIP_TRY(expr)                                                                     \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) return ::d377::fail(D377_ERR_HIP, #expr ": %s", hipGetErrorString(e_)); \
-  } while (0)
-
-// A per-device scratch area that kernels launched on ANY stream may use (the variable-base window
-// tables, the MSM workspace).  Users are serialised on the device: a launch first makes its stream wait
-// for the previous user's completion event and records its own afterwards, so two `_dev` calls on
-// different streams (or a host-path call on the context's private stream while a `_dev` launch is in
-// flight) queue up instead of racing.  Host-side access to this struct is under d377_ctx::mu.
-struct ScratchGuard {
-  hipEvent_t ev = nullptr;
-  bool used = false;
-  int init() { HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); return D377_OK; }
-  void destroy() { if (ev) (void)hipEventDestroy(ev); ev = nullptr; used = false; }
-  // A stream that is being captured into a hipGraph takes no part in the hand-over (an event recorded outside
-  // the capture cannot be waited on inside it): within the graph the launches keep their stream order.  What that
-  // means for a replay that overlaps other calls is area-specific: the lane-set areas (window tables, inversion
-  // records) are claimed atomically by every workgroup and never reset, so overlapping kernels simply share them;
-  // the MSM workspace is exclusive, and a caller who replays a graph containing an MSM while another MSM of the same
-  // device is in flight on a different stream must order the two (include/decaf377_amd.h, "Threads and streams").
-  static bool capturing(hipStream_t s) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
-  }
-  bool seen_capture = false;             // some launch on this area has been captured into a graph (see MsmWorkspace)
-  int acquire(hipStream_t s) {
-    if (capturing(s)) { seen_capture = true; return D377_OK; }
-    if (used) HIP_TRY(hipStreamWaitEvent(s, ev, 0));
-    return D377_OK;
-  }
-  int release(hipStream_t s) { if (capturing(s)) return D377_OK; HIP_TRY(hipEventRecord(ev, s)); used = true; return D377_OK; }
-  int drain() { if (used) HIP_TRY(hipEventSynchronize(ev)); return D377_OK; }   // before freeing the area
-};
-
-// Holds a scratch area for one launch: queues the launch behind the area's last user and records the hand-over event
-// on EVERY path out of the launch once the area has been acquired -- also when a later step of the launch fails, so
-// that the next user on another stream still queues behind whatever was enqueued.
-struct GuardScope {
-  ScratchGuard& g;
-  hipStream_t s;
-  bool held = false;
-  int acquire() { int rc = g.acquire(s); held = rc == D377_OK; return rc; }
-  // the success path hands over explicitly and reports a failed event record (the next user would not queue behind this
-  // launch); the destructor covers the error paths
-  int finish() { if (!held) return D377_OK; held = false; return g.release(s); }
-  ~GuardScope() { if (held) (void)g.release(s); }
-};
-
-// workspace of the multi-scalar multiplication (msm.hip), grow-only.  Once an MSM has been captured into a hipGraph the
-// graph holds pointers into the workspace it saw: from then on a workspace that is outgrown is retired (kept until the
-// context is destroyed) instead of freed, so a replay never touches freed memory.
-struct MsmWorkspace {
-  uint8_t* mem = nullptr;
-  size_t cap = 0;
-  ScratchGuard guard;
-  std::vector<uint8_t*> retired;
-};
 
 // The kernels that work in chunks and claim a lane set of the per-device scratch areas (d377.hip: dcb_claim).  At most
 // chunk_sets[k] workgroups of kernel k may be resident per CU -- that is how many lane sets it may claim; d377_ctx_create checks
@@ -100,11 +35,7 @@ struct DeviceState : PlanDev {               // (launch_plan.hpp: the CU count a
   int codec_chunked = -1;                // codec_chunked.hip: may its kernels claim lane sets (their residency matches them)?  -1 = not asked yet
   int msm_span_blocks = -1;              // msm.hip: workgroups of k_msm_spans a CU holds (occupancy query), -1 = not asked yet
   int dcb_sets = 0;                      // lane sets of the round-record area and its pool (the largest chunk_sets x CUs)
-  uint32_t* bm_scratch = nullptr;        // batch_msm.hip: tables and digit words of the batched small sums, per resident lane; grown on first use
-  size_t bm_cap = 0;
   int bm_lds[2] = {-1, -1};              // batch_msm.hip: LDS padding of its lane kernel (Element / Encoding form), -1 = not asked yet
-  uint8_t* bml_partials = nullptr;       // batch_msm_long.hip: the chains' partial sums and the fold levels' records; grown on demand, never shrunk
-  size_t bml_cap = 0;
   int bml_lds[2] = {-1, -1};             // batch_msm_long.hip: LDS padding of its lane kernel (Element / Encoding form), -1 = not asked yet
   int bmli_lds = -1;                     // batch_msm_long_indexed.hip: LDS padding of its lane kernel, -1 = not asked yet
   uint8_t* bmli_pool = nullptr;          // batch_msm_long_indexed.hip: the pool's staging area of the host form; grown on demand
@@ -127,8 +58,9 @@ struct DeviceState : PlanDev {               // (launch_plan.hpp: the CU count a
   uint32_t* starve_host = nullptr;       // pinned: the gave-up counter before / after a host-pointer call's kernels (StarveCheck)
   int vb_blocks = 0;
   uint32_t* inv_fail = nullptr;          // device counter of the -DD377_CHECK_INVARIANTS build (always allocated)
-  ScratchGuard vb_guard;
-  std::vector<void*> vb_retired;         // outgrown table scratch / partials areas a captured graph may still name: freed with the context (retire_scratch)
+  ScratchGuard vb_guard;                 // the lane-set areas and the two areas below
+  ScratchArea bm_scratch;                // batch_msm.hip: tables and digit words of the batched small sums, per resident lane; grown on first use
+  ScratchArea bml_partials;              // batch_msm_long.hip: the chains' partial sums and the fold levels' records; grown on demand, never shrunk
   hipStream_t stream = nullptr;          // compute stream of the host-pointer entry points
   hipStream_t copy_stream = nullptr;     // PCIe copies of the pipelined host path
   hipStream_t ctl_stream = nullptr;      // highest priority: d377_ctx_health / d377_ctx_reset_scratch (a hardware queue no kernel of ours waits in)
@@ -143,7 +75,8 @@ struct DeviceState : PlanDev {               // (launch_plan.hpp: the CU count a
   uint8_t* shard[4] = {nullptr, nullptr, nullptr, nullptr};
   size_t shard_cap[4] = {0, 0, 0, 0};
   hipEvent_t ev_shard = nullptr;
-  MsmWorkspace msm;
+  ScratchGuard msm_guard;
+  ScratchArea msm_ws;                    // msm.hip: the workspace of the multi-scalar multiplication, one per device
   SqrtTables tables() const { return SqrtTables{gtab, s_lookup, inv_fail}; }
 };
 
@@ -160,16 +93,6 @@ inline int ensure2(DeviceState& d, int slot, size_t bytes) { return grow(d.buf2[
 inline int ensure_shard(DeviceState& d, int slot, size_t bytes) { return grow(d.shard[slot], d.shard_cap[slot], bytes, bytes / 4 + 4096); }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// An outgrown scratch area of the lane-set guard (the Straus table scratch, the long sums' partials): freed -- unless a
-// launch on the guard's areas has been captured into a hipGraph, which then still holds the pointer: from then on the area
-// is retired and kept until d377_ctx_destroy, as the MSM workspace is (MsmWorkspace).  The caller has drained the guard.
-inline int retire_scratch(DeviceState& d, void* area) {
-  if (!area) return D377_OK;
-  if (d.vb_guard.seen_capture) d.vb_retired.push_back(area);
-  else HIP_TRY(hipFree(area));
-  return D377_OK;
-}
 
 // Synchronises a set of streams when the enclosing function returns with an error after work has been
 // enqueued: no copy into caller memory (or into a local vector) may still be in flight once we return.

@@ -1513,30 +1513,12 @@ int pick_window(const DeviceState& d, size_t n) {
   return (int)d.tuned(D377_TUNE_MSM_WINDOW, c);              // developer override: 4 .. 18 (>= 4: at most 63 windows, k_msm_final's table of cached sums)
 }
 
-// The workspace: grown when a call needs more (never inside a stream capture), handed from stream to stream by its guard.
-// `held` releases it on every path out of the caller, error or not.
-struct MsmHeld {
-  ScratchGuard& g; hipStream_t s; bool held;
-  int finish() { if (!held) return D377_OK; held = false; return g.release(s); }   // success path: a failed hand-over is an error
-  ~MsmHeld() { if (held) (void)g.release(s); }
-};
-int msm_reserve(DeviceState& d, hipStream_t s, size_t bytes, MsmHeld& held) {
-  int rc;
-  if (bytes > d.msm.cap) {
-    if (ScratchGuard::capturing(s))
-      return fail(D377_ERR_ARG, "%s", "msm: the workspace must grow, which cannot happen inside a stream capture -- run one MSM of this size before capturing");
-    if ((rc = d.msm.guard.drain())) return rc;          // a launch on another stream may still be using the old area
-    if (d.msm.mem) {
-      if (d.msm.guard.seen_capture) d.msm.retired.push_back(d.msm.mem);   // a captured graph may still point into it
-      else HIP_TRY(hipFree(d.msm.mem));
-    }
-    d.msm.mem = nullptr; d.msm.cap = 0;
-    HIP_TRY(hipMalloc(&d.msm.mem, bytes + bytes / 8));
-    d.msm.cap = bytes + bytes / 8;
-  }
-  if ((rc = d.msm.guard.acquire(s))) return rc;         // one workspace per device: queue behind its last user
-  held.held = true;
-  return D377_OK;
+// The workspace: grown when a call needs more (never inside a stream capture), handed from stream to stream by its guard:
+// one workspace per device, every call queues behind its last user (a GuardScope on d.msm_guard, acquired after this).
+int msm_reserve(DeviceState& d, hipStream_t s, size_t bytes) {
+  return d.msm_ws.reserve(d.msm_guard, s, bytes, SLACK_MSM_WORKSPACE,
+                          "msm: the workspace must grow, which cannot happen inside a stream capture -- run one MSM of this size before capturing",
+                          "msm: hipMalloc of the workspace failed (%zu bytes)");
 }
 
 // Batches up to this many points skip the buckets: a wave per 1 .. 3 points (Elements) or 1 .. 4 (Encodings), k_msm_tiny below.
@@ -1566,10 +1548,10 @@ int msm_launch_small(DeviceState& d, hipStream_t s, bool encoded, const void* pt
   if (per_wave < 1) per_wave = 1;
   const size_t waves = (n + per_wave - 1) / per_wave;
   const size_t m = tiny ? waves : (n + MS_QUADS - 1) / MS_QUADS;
-  MsmHeld held{d.msm.guard, s, false};
+  GuardScope held{d.msm_guard, s};
   int rc;
-  if ((rc = msm_reserve(d, s, m * PT_WORDS * 4, held))) return rc;
-  uint32_t* partial = (uint32_t*)d.msm.mem;
+  if ((rc = msm_reserve(d, s, m * PT_WORDS * 4)) || (rc = held.acquire())) return rc;
+  uint32_t* partial = d.msm_ws.as<uint32_t>();
   const SqrtTables T = d.tables();
   if (tiny && encoded) hipLaunchKernelGGL(k_msm_tiny<true>, dim3((unsigned)waves), dim3(64), 0, s, T, pts_in, scalars, n, (int)per_wave, partial, status);
   else if (tiny) hipLaunchKernelGGL(k_msm_tiny<false>, dim3((unsigned)waves), dim3(64), 0, s, T, pts_in, scalars, n, (int)per_wave, partial, status);
@@ -1584,7 +1566,7 @@ int msm_launch_small(DeviceState& d, hipStream_t s, bool encoded, const void* pt
 struct MsmCall { DeviceState& d; hipStream_t s; const MsmPlan& p; size_t n; };
 // region r of the workspace
 template <class T = uint32_t>
-T* msm_at(const MsmCall& c, MsmRegion r) { return reinterpret_cast<T*>(c.d.msm.mem + c.p.region[r].offset); }
+T* msm_at(const MsmCall& c, MsmRegion r) { return reinterpret_cast<T*>(c.d.msm_ws.as<uint8_t>() + c.p.region[r].offset); }
 
 // Phase 1: prepare (points -> affine records, scalars -> digits, written to `dig`) and the counting pass, for the digit type of
 // this window width
@@ -1771,8 +1753,8 @@ int msm_launch(DeviceState& d, hipStream_t s, bool encoded, const void* pts_in, 
   in.red = d.tuned(D377_TUNE_MSM_RED, PLAN_DEFAULT); in.skip = d.tuned(D377_TUNE_MSM_SKIP, PLAN_DEFAULT);
   in.chunked_sums = d.tuned(D377_TUNE_MSM_CHUNKED_SUMS, PLAN_DEFAULT); in.sort_packed = d.tuned(D377_TUNE_MSM_SORT_PACKED, PLAN_DEFAULT);
   const MsmPlan p = msm_plan(in);
-  MsmHeld held{d.msm.guard, s, false};
-  if ((rc = msm_reserve(d, s, p.bytes, held))) return rc;
+  GuardScope held{d.msm_guard, s};
+  if ((rc = msm_reserve(d, s, p.bytes)) || (rc = held.acquire())) return rc;
   const MsmCall call{d, s, p, n};
   if ((rc = p.wide_digits ? msm_prepare_count<int32_t>(call, encoded, pts_in, scalars, status)
                           : msm_prepare_count<int16_t>(call, encoded, pts_in, scalars, status))) return rc;

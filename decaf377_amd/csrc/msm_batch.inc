@@ -163,8 +163,8 @@ int bsum_launch(DeviceState& d, hipStream_t s, bool encoded, const void* pts_in,
   int rc;
   if ((rc = msm_span_blocks(d))) return rc;
   const BsumPlan bp = bsum_plan_for(d, n, m, window_bits);
-  MsmHeld held{d.msm.guard, s, false};
-  if ((rc = msm_reserve(d, s, bp.bytes, held))) return rc;
+  GuardScope held{d.msm_guard, s};
+  if ((rc = msm_reserve(d, s, bp.bytes)) || (rc = held.acquire())) return rc;
   const size_t rec = encoded ? 32 : 128;
   for (size_t pass = 0; pass < bp.passes; ++pass) {
     const size_t lo = pass * bp.sums_per_pass, K = pass + 1 < bp.passes ? bp.sums_per_pass : bp.last_sums;

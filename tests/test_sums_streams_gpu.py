@@ -49,7 +49,7 @@ TUNING = {"tiny_max": 0, "msm_small_max": 0}
 # call (stream form) -> (guard, shape-dependent area): read off the launch functions (batch_msm.hip: batch_msm_launch,
 # batch_msm_mixed.hip: mixed_launch, batch_msm_long.hip: batch_msm_long_launch, batch_msm_long_indexed.hip:
 # batch_msm_long_indexed_launch, fixed_bases.hip: fixed_msm_launch / fixed_msm_long_launch, msm.hip: msm_reserve,
-# msm_batch.inc: bsum_launch).  "vb" = DeviceState::vb_guard, "msm" = MsmWorkspace::guard.
+# msm_batch.inc: bsum_launch).  "vb" = DeviceState::vb_guard, "msm" = DeviceState::msm_guard.
 GUARD_OF = {
     "d377_batch_msm_small_dev": ("vb", "table scratch (m tables per lane)"),
     "d377_batch_msm_small_encoded_dev": ("vb", "table scratch (m tables per lane)"),
