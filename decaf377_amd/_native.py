@@ -62,6 +62,11 @@ BUCKET_SUMS_EXPORTS = [
     "d377_batch_bucket_msm", "d377_batch_bucket_msm_encoded", "d377_batch_bucket_msm_resident",
     "d377_batch_bucket_msm_encoded_resident", "d377_bucket_msm_plan",
 ]
+# every symbol include/decaf377_amd_ragged_sums.h declares (checked by tests/test_ragged_sums_host.py)
+RAGGED_SUMS_EXPORTS = [
+    "d377_batch_ragged_msm", "d377_batch_ragged_msm_encoded", "d377_batch_ragged_msm_resident",
+    "d377_batch_ragged_msm_encoded_resident", "d377_ragged_msm_plan",
+]
 
 
 class CtxOpts(ctypes.Structure):
@@ -252,6 +257,14 @@ def load():
         "d377_batch_bucket_msm_resident": [vp, i32, vp, vp, vp, sz, sz, i32, vp, vp],
         "d377_batch_bucket_msm_encoded_resident": [vp, i32, vp, vp, vp, sz, sz, i32, vp, vp, vp],
         "d377_bucket_msm_plan": [vp, i32, sz, sz, i32, ctypes.POINTER(i32), u64p, u64p, u64p],
+    })
+    # many sums of any length each, by offsets (decaf377_amd_ragged_sums.h): host forms, resident forms, the plan
+    resident.update({
+        "d377_batch_ragged_msm": [vp, vp, vp, vp, sz, i32, vp, vp],
+        "d377_batch_ragged_msm_encoded": [vp, vp, vp, vp, sz, i32, vp, vp, vp],
+        "d377_batch_ragged_msm_resident": [vp, i32, vp, vp, vp, vp, vp, sz, i32, vp, vp],
+        "d377_batch_ragged_msm_encoded_resident": [vp, i32, vp, vp, vp, vp, vp, sz, i32, vp, vp, vp],
+        "d377_ragged_msm_plan": [vp, i32, vp, sz, i32, ctypes.POINTER(i32), u64p, u64p, u64p, u64p],
     })
     for name, args in resident.items():
         getattr(lib, name).argtypes = args

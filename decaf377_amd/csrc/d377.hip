@@ -1528,7 +1528,7 @@ void free_device(DeviceState& d) {
     if (d.ev_done[i]) (void)hipEventDestroy(d.ev_done[i]);
   }
   if (d.ev_shard) (void)hipEventDestroy(d.ev_shard);
-  d.bm_scratch.release(); d.bml_partials.release(); d.msm_ws.release();
+  d.bm_scratch.release(); d.bml_partials.release(); d.msm_ws.release(); d.rsum_offsets.release();
   d.vb_guard.destroy();                    // (with the blocks retired under it)
   d.msm_guard.destroy();
   if (d.copy_stream) (void)hipStreamDestroy(d.copy_stream);

@@ -77,6 +77,7 @@ struct DeviceState : PlanDev {               // (launch_plan.hpp: the CU count a
   hipEvent_t ev_shard = nullptr;
   ScratchGuard msm_guard;
   ScratchArea msm_ws;                    // msm.hip: the workspace of the multi-scalar multiplication, one per device
+  ScratchArea rsum_offsets;              // msm_ragged.inc: the offsets a host form of the ragged sums uploads (under msm_guard); grown on demand
   SqrtTables tables() const { return SqrtTables{gtab, s_lookup, inv_fail}; }
 };
 

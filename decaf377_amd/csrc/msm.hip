@@ -1906,3 +1906,5 @@ int d377_sum_elements_dev(d377_ctx* ctx, int dev, void* stream, const uint64_t* 
 
 // d377_batch_bucket_msm: many sums through one run of the pipeline above per pass (kernels, launcher, C entry points)
 #include "msm_batch.inc"
+// d377_batch_ragged_msm: the same pass with the term -> sum map taken from offsets (any length per sum)
+#include "msm_ragged.inc"

@@ -126,16 +126,27 @@ k_bsum_final(const uint32_t* sums, WinShape ws, int K, uint8_t* enc_out, uint64_
 }
 
 // ------------------------------------------------------------------------------ host side ---
-// one pass: K sums of m terms under plan p (msm_plan with sums = K), in the workspace the caller holds
-template <class DT>
-int bsum_pass(DeviceState& d, hipStream_t s, const MsmPlan& p, bool encoded, const void* pts_in, const uint8_t* scalars, size_t m, size_t K,
+// Which term belongs to which sum, the one thing a pass needs to know about the lengths: the points of a pass of K sums and
+// the launch of its keys kernel.  Equal lengths here; offsets in msm_ragged.inc (RsumOffsets).
+struct BsumEqual {
+  size_t m;
+  size_t points(size_t K) const { return K * m; }
+  template <class DT>
+  void keys(DeviceState& d, hipStream_t s, const int16_t* dig, size_t N, size_t, int W, int c, DT* out) const {
+    hipLaunchKernelGGL(k_bsum_keys<DT>, dim3(grid_of(d, N)), dim3(BLOCK), 0, s, dig, N, m, W, c, out);
+  }
+};
+
+// one pass: K sums, their terms dealt by `map`, under plan p (msm_plan with sums = K), in the workspace the caller holds
+template <class DT, class Map>
+int bsum_pass(DeviceState& d, hipStream_t s, const MsmPlan& p, bool encoded, const void* pts_in, const uint8_t* scalars, const Map& map, size_t K,
               uint8_t* enc_out, uint64_t* xyzt_out, uint8_t* status) {
-  const size_t N = K * m;
+  const size_t N = map.points(K);
   const MsmCall call{d, s, p, N};
   int rc;
   int16_t* dig = msm_at<int16_t>(call, R_IDX);                  // the plain digits: W N int16 in a region of W N words
   if ((rc = msm_prepare<int16_t>(call, encoded, pts_in, scalars, status, dig))) return rc;
-  hipLaunchKernelGGL(k_bsum_keys<DT>, dim3(grid_of(d, N)), dim3(BLOCK), 0, s, dig, N, m, p.W, p.shape.c, msm_at<DT>(call, R_DIGITS));
+  map.template keys<DT>(d, s, dig, N, K, p.W, p.shape.c, msm_at<DT>(call, R_DIGITS));
   if ((rc = msm_count<DT>(call))) return rc;
   if ((rc = msm_scan_place(call))) return rc;
   if ((rc = msm_bucket_records(call))) return rc;
@@ -172,8 +183,8 @@ int bsum_launch(DeviceState& d, hipStream_t s, bool encoded, const void* pts_in,
     const uint8_t* pts = (const uint8_t*)pts_in + lo * m * rec;
     uint64_t* xo = xyzt_out ? xyzt_out + lo * 16 : nullptr;
     uint8_t* st = status ? status + lo * m : nullptr;
-    rc = p.wide_digits ? bsum_pass<int32_t>(d, s, p, encoded, pts, scalars + lo * m * 32, m, K, enc_out + lo * 32, xo, st)
-                       : bsum_pass<int16_t>(d, s, p, encoded, pts, scalars + lo * m * 32, m, K, enc_out + lo * 32, xo, st);
+    rc = p.wide_digits ? bsum_pass<int32_t>(d, s, p, encoded, pts, scalars + lo * m * 32, BsumEqual{m}, K, enc_out + lo * 32, xo, st)
+                       : bsum_pass<int16_t>(d, s, p, encoded, pts, scalars + lo * m * 32, BsumEqual{m}, K, enc_out + lo * 32, xo, st);
     if (rc) return rc;
   }
   return held.finish();

@@ -109,6 +109,11 @@ def _is_u8(a):
     return a.dtype == np.uint8
 
 
+def _u64_dtypes():
+    import torch
+    return (torch.int64, torch.uint64)
+
+
 def _ptr(a):
     """The void* argument for an array of either kind, which the caller keeps alive through the call; None is NULL."""
     if a is None:
@@ -662,6 +667,13 @@ class Context:
         if m < 1 or terms % m:
             raise ValueError("%s: " % what + "the number of points must be a multiple of m")
         n = terms // m
+        return self._sums(what, host_names, device_names, points, scalar32, encoded, terms, n, outs, elements,
+                          lambda dev: (ctypes.c_size_t(m), ctypes.c_size_t(n), *extra), stage_foreign)
+
+    def _sums(self, what, host_names, device_names, points, scalar32, encoded, terms, n, outs, elements, mid, stage_foreign=True):
+        """The staging, the outputs and the launch of n sums over `terms` rows of `points`, Encodings if `encoded`, for
+        _sums_of_m and msm_ragged; mid(dev): the call's own arguments between the scalars and the outputs, for the route
+        taken (dev None: the host form)."""
         tdev = points.device if _is_torch(points) else None
         _check(points, ENC if encoded else ELEM, terms, what + " points")
         _check(scalar32, ENC, terms, what + " scalars", tdev)
@@ -683,8 +695,7 @@ class Context:
                         _check(a, spec, rows, what + " output", tdev)
             pts, sc = _staged(None, points), _staged(None, scalar32)
             res = outs if outs is not None and tdev is None else _outputs(what, None, n, elements, status_rows)
-        self._launch(dev, host_names[encoded], device_names[encoded], _ptr(pts), _ptr(sc), ctypes.c_size_t(m), ctypes.c_size_t(n),
-                     *extra, *_out_ptrs(res, elements))
+        self._launch(dev, host_names[encoded], device_names[encoded], _ptr(pts), _ptr(sc), *mid(dev), *_out_ptrs(res, elements))
         return _results(res, dev, (points,), into=outs)
 
     def msm_buckets(self, points, scalar32, m, outs=None, elements=False, window_bits=0):
@@ -706,6 +717,69 @@ class Context:
         _native.check(self._lib.d377_bucket_msm_plan(self._h, int(dev), ctypes.c_size_t(int(n)), ctypes.c_size_t(int(m)), int(window_bits),
                                                      ctypes.byref(c), ctypes.byref(spp), ctypes.byref(passes), ctypes.byref(ws)))
         return {"window_bits": c.value, "sums_per_pass": spp.value, "passes": passes.value, "workspace_bytes": ws.value}
+
+    @staticmethod
+    def _offsets(what, offsets):
+        """`offsets` as a contiguous uint64 array on the host: n + 1 values that start at 0 and never decrease."""
+        off = np.asarray(offsets.detach().cpu().numpy() if _is_torch(offsets) else offsets)
+        if off.ndim != 1 or off.size < 1 or off.dtype.kind not in "iu":
+            raise ValueError(what + ": offsets must be n + 1 integers")
+        if off.dtype.kind == "i" and (off < 0).any():
+            raise ValueError(what + ": offsets must not be negative")
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        if off[0] != 0 or (off[1:] < off[:-1]).any():
+            raise ValueError(what + ": offsets must start at 0 and never decrease")
+        return off
+
+    def msm_ragged(self, points, scalar32, offsets, outs=None, elements=False, window_bits=0, offsets_dev=None):
+        """n independent multiscalar sums of ANY length each, 0 .. 2^20 terms per sum, by the bucket method
+        (d377_batch_ragged_msm[_encoded], include/decaf377_amd_ragged_sums.h): sum i is the terms offsets[i] ..
+        offsets[i + 1] - 1 of points [terms, 16] u64 Elements or [terms, 32] u8 Encodings and scalar32 [terms, 32].  offsets:
+        n + 1 integers on the host (anything numpy turns into int64 or uint64), offsets[0] == 0, never decreasing,
+        offsets[n] == terms.  Results, outs and routing are msm_buckets's; status has offsets[n] rows; an empty sum gives the
+        all-zero Encoding.  Tensors on a device of the context take the resident form on torch's current stream (one eager
+        call of a shape before capturing it in a graph).  offsets_dev: the same n + 1 values as a uint64 / int64 tensor on
+        that device, which the kernels read.  When it is None THIS METHOD ALLOCATES A TENSOR AND COPIES THE OFFSETS TO THE
+        DEVICE, which a stream capture does not allow: a caller who captures a graph passes its own.  Nothing checks that
+        offsets_dev holds the values of offsets; if it does not, the sums are wrong (memory stays safe).
+        window_bits: 0 = the library's width rule on the mean length; 4 .. 16 forces the window width."""
+        what = "msm_ragged"
+        off = self._offsets(what, offsets)
+        n = int(off.size) - 1
+        if points.ndim != 2 or int(points.shape[1]) not in (16, 32):
+            raise ValueError(what + ": points must be [terms, 16] Elements or [terms, 32] Encodings")
+        encoded, terms = int(points.shape[1]) == 32, _rows(points)
+        if terms != int(off[n]):
+            raise ValueError(what + ": offsets[n] = %d, but there are %d points" % (int(off[n]), terms))
+        held = []                                                # keeps the uploaded offsets alive through the call
+
+        def mid(dev):
+            args = [_ptr(off)]
+            if dev is not None:
+                od = offsets_dev
+                if od is None:
+                    od = _on_device(dev, off)
+                elif not (_is_torch(od) and od.device == dev and od.dtype in _u64_dtypes() and tuple(od.shape) == (n + 1,)
+                          and od.is_contiguous()):
+                    raise ValueError(what + ": offsets_dev must be a contiguous [n + 1] uint64/int64 tensor on the points' device")
+                held.append(od)
+                args.append(_ptr(od))
+            return (*args, ctypes.c_size_t(n), ctypes.c_int(int(window_bits)))
+
+        return self._sums(what, ("d377_batch_ragged_msm", "d377_batch_ragged_msm_encoded"),
+                          ("d377_batch_ragged_msm_resident", "d377_batch_ragged_msm_encoded_resident"), points, scalar32, encoded, terms, n, outs,
+                          elements, mid)
+
+    def msm_ragged_plan(self, offsets, window_bits=0, dev=0):
+        """The plan of msm_ragged for the sums `offsets` delimits on device `dev` of the context (d377_ragged_msm_plan) ->
+        {"window_bits", "passes", "max_sums_per_pass", "max_points_per_pass", "workspace_bytes"}."""
+        off = self._offsets("msm_ragged_plan", offsets)
+        c = ctypes.c_int(0)
+        v = [ctypes.c_uint64(0) for _ in range(4)]
+        _native.check(self._lib.d377_ragged_msm_plan(self._h, int(dev), _ptr(off), ctypes.c_size_t(int(off.size) - 1), int(window_bits),
+                                                     ctypes.byref(c), *(ctypes.byref(x) for x in v)))
+        return {"window_bits": c.value, "passes": v[0].value, "max_sums_per_pass": v[1].value, "max_points_per_pass": v[2].value,
+                "workspace_bytes": v[3].value}
 
     def msm_long_indexed(self, pool, point_index, scalar32, m, elements=False, check_indices=True, outs=None):
         """n sums of m terms that name their points in a shared pool (d377_batch_long_msm_indexed):

@@ -588,6 +588,36 @@ class Engine {
                                                  m, n, window_bits, reinterpret_cast<uint8_t*>(enc_out), reinterpret_cast<uint64_t*>(elements_out),
                                                  status));
   }
+  /// MANY sums of ANY length each, 0 .. 2^20 terms per sum (d377_batch_ragged_msm, decaf377_amd_ragged_sums.h): sum i is the terms
+  /// offsets[i] .. offsets[i + 1] - 1; offsets holds n + 1 values, starts at 0, never decreases and ends at points.size().  An
+  /// empty sum is the identity.  No short-sum route: see the header's "which call where".  window_bits as above.
+  std::vector<Element> vartime_multiscalar_mul_batch_ragged(const std::vector<uint64_t>& offsets, const std::vector<Fr>& scalars,
+                                                            const std::vector<Element>& points, std::vector<Encoding>* encodings = nullptr,
+                                                            int window_bits = 0) {
+    if (scalars.size() != points.size() || offsets.empty() || offsets.back() != points.size()) throw std::invalid_argument("length mismatch");
+    std::vector<Element> out(offsets.size() - 1);
+    std::vector<Encoding> enc(out.size());
+    check(d377_batch_ragged_msm(ctx_, u64(points), u8(scalars), offsets.data(), out.size(), window_bits, u8m(enc),
+                                reinterpret_cast<uint64_t*>(out.data())));
+    if (encodings) *encodings = std::move(enc);
+    return out;
+  }
+  /// ... on DEVICE pointers of device `dev` of the Engine (records 16-byte aligned): enqueues on `stream` and returns.  `offsets`
+  /// (n + 1 values, HOST memory) is read before the call returns; the kernels read `offsets_dev`, the same values on the device
+  /// (8-byte aligned).  Nothing can check that the two agree: if they do not, the sums are wrong (memory stays safe).  One eager
+  /// call of a shape must come before it is captured into a graph.
+  void msm_ragged_resident(int dev, void* stream, const Element* points, const Fr* scalars, const uint64_t* offsets, const uint64_t* offsets_dev,
+                           size_t n, Encoding* enc_out, Element* elements_out = nullptr, int window_bits = 0) {
+    check(d377_batch_ragged_msm_resident(ctx_, dev, stream, reinterpret_cast<const uint64_t*>(points), reinterpret_cast<const uint8_t*>(scalars),
+                                         offsets, offsets_dev, n, window_bits, reinterpret_cast<uint8_t*>(enc_out),
+                                         reinterpret_cast<uint64_t*>(elements_out)));
+  }
+  void msm_ragged_resident(int dev, void* stream, const Encoding* points, const Fr* scalars, const uint64_t* offsets, const uint64_t* offsets_dev,
+                           size_t n, Encoding* enc_out, Element* elements_out, uint8_t* status, int window_bits = 0) {
+    check(d377_batch_ragged_msm_encoded_resident(ctx_, dev, stream, reinterpret_cast<const uint8_t*>(points), reinterpret_cast<const uint8_t*>(scalars),
+                                                 offsets, offsets_dev, n, window_bits, reinterpret_cast<uint8_t*>(enc_out),
+                                                 reinterpret_cast<uint64_t*>(elements_out), status));
+  }
   /// CurveGroup::normalize_batch (src/ark_curve/element.rs:74-81): affine (x, y) as 4 Montgomery limbs each
   std::vector<std::array<uint64_t, 8>> normalize_batch(const std::vector<Element>& p) {
     std::vector<std::array<uint64_t, 8>> out(p.size());

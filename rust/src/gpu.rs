@@ -40,6 +40,8 @@ pub mod ffi_resident;                                             // rust/src/ff
 pub mod ffi_long_sums;                                            // rust/src/ffi_long_sums.rs, from include/decaf377_amd_long_sums.h
 #[path = "gpu/ffi_bucket_sums.rs"]
 pub mod ffi_bucket_sums;                                          // rust/src/ffi_bucket_sums.rs, from include/decaf377_amd_bucket_sums.h
+#[path = "gpu/ffi_ragged_sums.rs"]
+pub mod ffi_ragged_sums;                                          // rust/src/ffi_ragged_sums.rs, from include/decaf377_amd_ragged_sums.h
 
 /// Which backend's root `sqrt_ratio_zeta_batch` returns (the flags are the same).
 #[derive(Copy, Clone, Debug, PartialEq, Eq)]
@@ -568,6 +570,27 @@ impl Element {
         })?;
         Ok((out.chunks_exact(16).map(element_from_xyzt).collect(), enc))
     }
+    /// MANY sums of ANY length each, 0 ..= 2^20 terms per sum (d377_batch_ragged_msm): sum i is the terms offsets[i] ..
+    /// offsets[i + 1] of `scalars` and `points`; offsets has n + 1 entries, starts at 0, never decreases and ends at
+    /// points.len().  An empty sum is the identity.  The bucket pipeline of `vartime_multiscalar_mul_batch_buckets_gpu` with the
+    /// sum of a term looked up in the offsets: no short-sum route, so pad and use the indexed long sums when most sums are short.
+    pub fn vartime_multiscalar_mul_batch_ragged_gpu(ctx: &GpuContext, offsets: &[usize], scalars: &[Fr], points: &[Element])
+        -> Result<(Vec<Element>, Vec<Encoding>), GpuError> {
+        assert_eq!(scalars.len(), points.len());
+        assert!(!offsets.is_empty() && offsets[0] == 0 && offsets[offsets.len() - 1] == points.len());
+        assert!(offsets.windows(2).all(|w| w[0] <= w[1]));
+        let n = offsets.len() - 1;
+        let off: Vec<u64> = offsets.iter().map(|&o| o as u64).collect();
+        let xyzt = elements_to_xyzt(points);
+        let bytes = pack32(scalars, |k| k.to_bytes());
+        let mut enc = vec![Encoding([0u8; 32]); n];
+        let mut out = vec![0u64; 16 * n];
+        check(unsafe {
+            ffi_ragged_sums::d377_batch_ragged_msm(ctx.0, xyzt.as_ptr(), bytes.as_ptr(), off.as_ptr(), n, 0, enc.as_mut_ptr() as *mut u8,
+                                                   out.as_mut_ptr())
+        })?;
+        Ok((out.chunks_exact(16).map(element_from_xyzt).collect(), enc))
+    }
     /// Long sums whose terms name their points: sum i = sum over j < m of scalars[i m + j] * pool[point_index[i m + j]]
     /// (d377_batch_long_msm_indexed).  -1 is an absent term; any other index outside the pool is refused before any launch.
     pub fn vartime_multiscalar_mul_batch_long_indexed_gpu(ctx: &GpuContext, m: usize, pool: &[Element], point_index: &[i32], scalars: &[Fr])
@@ -811,5 +834,23 @@ pub mod dev {
                                                status: *mut u8) -> Result<(), GpuError> {
         check(ffi_bucket_sums::d377_batch_bucket_msm_encoded_resident(ctx.0, dev, stream, enc32, scalar32, m, n, window_bits, enc32_out,
                                                                       xyzt_out, status))
+    }
+
+    // Many sums of any length each on device buffers (ffi_ragged_sums.rs): `offsets` (n + 1 values, HOST memory) is read before
+    // the call returns, the kernels read `offsets_dev` (the same values on the device, 8-byte aligned); nothing can check that
+    // the two agree.  `xyzt_out` may be null; window_bits 0 = the library's rule.  One eager call of a shape before a capture.
+    pub unsafe fn msm_ragged_resident(ctx: &GpuContext, dev: i32, stream: *mut c_void, xyzt: *const u64, scalar32: *const u8,
+                                      offsets: &[u64], offsets_dev: *const u64, window_bits: i32, enc32_out: *mut u8, xyzt_out: *mut u64)
+        -> Result<(), GpuError> {
+        assert!(!offsets.is_empty());
+        check(ffi_ragged_sums::d377_batch_ragged_msm_resident(ctx.0, dev, stream, xyzt, scalar32, offsets.as_ptr(), offsets_dev,
+                                                              offsets.len() - 1, window_bits, enc32_out, xyzt_out))
+    }
+    pub unsafe fn msm_ragged_encoded_resident(ctx: &GpuContext, dev: i32, stream: *mut c_void, enc32: *const u8, scalar32: *const u8,
+                                              offsets: &[u64], offsets_dev: *const u64, window_bits: i32, enc32_out: *mut u8,
+                                              xyzt_out: *mut u64, status: *mut u8) -> Result<(), GpuError> {
+        assert!(!offsets.is_empty());
+        check(ffi_ragged_sums::d377_batch_ragged_msm_encoded_resident(ctx.0, dev, stream, enc32, scalar32, offsets.as_ptr(), offsets_dev,
+                                                                      offsets.len() - 1, window_bits, enc32_out, xyzt_out, status))
     }
 }
