@@ -446,9 +446,17 @@ constexpr int MSM_MAX_WINDOW = 18;                                     // widest
 constexpr int MAX_SUPER = ((1 << (MSM_MAX_WINDOW - 1)) + 1 + SUPER - 1) / SUPER;   // 1 025 super-buckets at 18 bits
 constexpr int MAX_BINS = MAX_SUPER > SUPER ? MAX_SUPER : SUPER;
 constexpr int TILE_PER_THREAD = 8, TILE = SORT_THREADS * TILE_PER_THREAD;
+constexpr int SORT_WAVES = SORT_THREADS / 64;
 struct TileLds {
-  uint32_t idx[TILE];                  // the tile's entries, sorted by bin
-  uint16_t bin[TILE];
+  union {
+    struct {
+      uint32_t idx[TILE];              // the tile's entries, sorted by bin
+      uint16_t bin[TILE];
+    };
+    // ORDERED only.  Before the tile is staged, the same memory: entries of this tile per (wave, bin), each row written by its
+    // wave alone (zero between tiles); after the prefix, where the wave's entries of a bin start within the tile's run of it.
+    uint16_t wcount[SORT_WAVES][MAX_BINS];
+  };
   uint8_t sub[TILE];
   uint32_t hist[MAX_BINS];             // entries of this tile per bin (zero between tiles)
   uint32_t start[MAX_BINS];            // first staged position of a bin
@@ -464,10 +472,22 @@ struct TileLds {
 // unconditional; without it (level 2: a super-bucket is two or three tiles) a tile fetches its own entries and only its
 // real entries are stored -- there the clamped repeats of a part-filled last tile cost more than the order saves (measured:
 // 155 -> 190 us at 2^22 with AHEAD, against 334 -> 250 us for level 1).
-template <bool HAS_SUB, bool AHEAD, class Load, class Decode>
+// ORDERED: the place of an entry among the tile's entries of its bin is a function of the tile alone, so that the sorted order,
+// the order of a bucket's additions and with it the BYTES of a sum's Element record are a function of the inputs; the sums by
+// buckets ask for it when they return records (msm_batch.inc bsum_pass).  Without it an LDS atomic per entry hands the places
+// out in the order the atomics arrive -- two runs may sum a bucket in two orders and return two projective representatives of
+// one group element -- which is faster and is all an Encoding needs: d377_msm and every call without records keep it.
+template <bool HAS_SUB, bool AHEAD, bool ORDERED, class Load, class Decode>
 __device__ __forceinline__ void tile_scatter(TileLds& L, size_t lo, size_t hi, int nbins, Load load, Decode decode, uint32_t* out_idx, uint8_t* out_sub) {
-  const int t = threadIdx.x;
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
   if (lo >= hi) return;
+  static_assert(sizeof(L.wcount) <= sizeof(L.idx) + sizeof(L.bin), "the waves' counters live where the staged tile goes");
+  const uint64_t below = (1ull << lane) - 1;
+  int nbits = 0;
+  if (ORDERED) {
+    while ((1 << nbits) < nbins) ++nbits;                           // ballots that tell two bins apart
+    for (int b = lane; b < nbins; b += 64) L.wcount[wave][b] = 0;
+  }
   // The NEXT tile's entries are requested before this tile's stores go out, and every access is unconditional (clamped to
   // the range): the kernels spend three quarters of their wave cycles waiting for memory (SQ_WAIT_ANY 0.76 / 0.65 of
   // SQ_WAVE_CYCLES, VALU busy 0.05: profiles/r05_stall_reasons_msm_2^22.txt), and a tile that starts by fetching its
@@ -496,13 +516,45 @@ __device__ __forceinline__ void tile_scatter(TileLds& L, size_t lo, size_t hi, i
     // (Ranking the lanes of a wave that share a bin with one ballot per bin bit and a single LDS atomic per group was
     // built and measured: 318 -> 468 us and 228 -> 420 us for the two levels at 2^22 -- the returning atomics are not what
     // these kernels wait for.)
+    if (!ORDERED) {
 #pragma unroll
-    for (int r = 0; r < TILE_PER_THREAD; ++r) {
+      for (int r = 0; r < TILE_PER_THREAD; ++r) {
+        const size_t i = tile_lo + (size_t)r * SORT_THREADS + t;
+        bin[r] = -1;
+        if (i < hi && decode(raw[r], i, &pay[r], &bin[r], &sub[r])) rank[r] = atomicAdd(&L.hist[bin[r]], 1u); else bin[r] = -1;
+      }
+    }
+    // ORDERED: by wave, then by the thread's round r, then by lane.  The lanes of a wave that share a bin find each other with
+    // one ballot per bin bit; the first of them moves the wave's own counter, which no other wave touches, so there is no
+    // atomic and no order between waves to depend on.
+#pragma unroll
+    for (int r = 0; ORDERED && r < TILE_PER_THREAD; ++r) {
       const size_t i = tile_lo + (size_t)r * SORT_THREADS + t;
       bin[r] = -1;
-      if (i < hi && decode(raw[r], i, &pay[r], &bin[r], &sub[r])) rank[r] = atomicAdd(&L.hist[bin[r]], 1u); else bin[r] = -1;
+      const bool ok = i < hi && decode(raw[r], i, &pay[r], &bin[r], &sub[r]);
+      if (!ok) bin[r] = -1;
+      uint64_t peers = __ballot(ok);
+      for (int k = 0; k < nbits; ++k) {
+        const bool bit = ok && ((bin[r] >> k) & 1) != 0;
+        const uint64_t m = __ballot(bit);
+        peers &= bit ? m : ~m;
+      }
+      if (ok) {
+        const uint32_t old = L.wcount[wave][bin[r]];
+        rank[r] = old + (uint32_t)__popcll(peers & below);
+        if ((peers & below) == 0) L.wcount[wave][bin[r]] = (uint16_t)(old + (uint32_t)__popcll(peers));
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // the next round reads what this round's first lanes wrote
     }
     __syncthreads();
+    if (ORDERED) {
+      for (int b = t; b < nbins; b += SORT_THREADS) {               // a thread per bin: the waves' parts of the bin in wave order
+        uint32_t h = 0;
+        for (int w = 0; w < SORT_WAVES; ++w) { const uint32_t c = L.wcount[w][b]; L.wcount[w][b] = (uint16_t)h; h += c; }
+        L.hist[b] = h;
+      }
+      __syncthreads();
+    }
     if (t < 64) {                                                   // one wave: exclusive prefix over the bins
       const int K = (nbins + 63) / 64, b0 = t * K;
       uint32_t own = 0;
@@ -526,8 +578,12 @@ __device__ __forceinline__ void tile_scatter(TileLds& L, size_t lo, size_t hi, i
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < TILE_PER_THREAD; ++r)
+      if (bin[r] >= 0) rank[r] += L.start[bin[r]] + (ORDERED ? L.wcount[wave][bin[r]] : 0u);      // the entry's place in the staged tile
+    if (ORDERED) __syncthreads();                                   // (the counters are read: their memory takes the staged entries)
+#pragma unroll
+    for (int r = 0; r < TILE_PER_THREAD; ++r)
       if (bin[r] >= 0) {
-        const uint32_t p = L.start[bin[r]] + rank[r];
+        const uint32_t p = rank[r];
         L.idx[p] = pay[r]; L.bin[p] = (uint16_t)bin[r];
         if (HAS_SUB) L.sub[p] = (uint8_t)sub[r];
       }
@@ -567,12 +623,14 @@ __device__ __forceinline__ void tile_scatter(TileLds& L, size_t lo, size_t hi, i
       }
     }
     __syncthreads();
+    if (ORDERED)
+      for (int b = lane; b < nbins; b += 64) L.wcount[wave][b] = 0;  // (the staged entries are stored: the wave's counters for the next tile)
   }
 }
 
 // (PACKED, batches of up to PACKED_MAX_POINTS points: the level-1 entry is ONE word, msm_plan.hpp)
 // (TileLds is 73 KiB with bins for 18-bit windows: beyond the 64 KiB of static LDS, so both levels take it as dynamic LDS)
-template <bool PACKED, class DT>
+template <bool PACKED, class DT, bool ORDERED>
 __global__ void __launch_bounds__(SORT_THREADS) k_msm_place1(const DT* digits, size_t n, int nb, int S, size_t per,
                                                              const uint32_t* blockhist, const uint32_t* offs,
                                                              uint32_t* tmp_idx, uint8_t* tmp_sub) {
@@ -592,7 +650,7 @@ __global__ void __launch_bounds__(SORT_THREADS) k_msm_place1(const DT* digits, s
   __syncthreads();
   const size_t lo = (size_t)sl * per, hi = (lo + per < n) ? lo + per : n;
   const DT* dw = digits + (size_t)w * n;
-  tile_scatter<!PACKED, true>(L, lo, hi, nsuper,
+  tile_scatter<!PACKED, true, ORDERED>(L, lo, hi, nsuper,
                      [dw](size_t i) { return (uint64_t)(uint32_t)(int32_t)dw[i]; },
                      [](uint64_t raw, size_t i, uint32_t* pay, int* bin, uint32_t* sub) {
                        const int d = (int32_t)(uint32_t)raw;
@@ -608,7 +666,7 @@ __global__ void __launch_bounds__(SORT_THREADS) k_msm_place1(const DT* digits, s
 }
 
 // workgroup (window, super-bucket): its entries are contiguous in tmp_*, at the positions the bucket runs will occupy
-template <bool PACKED>
+template <bool PACKED, bool ORDERED>
 __global__ void __launch_bounds__(SORT_THREADS) k_msm_place2(const uint32_t* tmp_idx, const uint8_t* tmp_sub, size_t n, int nb,
                                                              const uint32_t* offs, uint32_t* idx) {
   extern __shared__ uint8_t tile_lds_[];
@@ -621,7 +679,7 @@ __global__ void __launch_bounds__(SORT_THREADS) k_msm_place2(const uint32_t* tmp
   __syncthreads();
   const uint32_t* ti = tmp_idx + (size_t)w * n;
   const uint8_t* ts = tmp_sub + (size_t)w * n;
-  tile_scatter<false, false>(L, ow[first], ow[last], SUPER,
+  tile_scatter<false, false, ORDERED>(L, ow[first], ow[last], SUPER,
                       [ti, ts](size_t i) { return PACKED ? (uint64_t)ti[i] : ((uint64_t)ti[i] | ((uint64_t)ts[i] << 32)); },
                       [](uint64_t raw, size_t, uint32_t* pay, int* bin, uint32_t* sub) {
                         if (PACKED) {
@@ -1563,7 +1621,8 @@ int msm_launch_small(DeviceState& d, hipStream_t s, bool encoded, const void* pt
 }
 
 // ---- the bucket method's launcher: msm_plan.hpp decides every route, size and offset; the three phases below launch ----------
-struct MsmCall { DeviceState& d; hipStream_t s; const MsmPlan& p; size_t n; };
+// ordered: the sort places a bucket's points in an order that is a function of the inputs (tile_scatter ORDERED)
+struct MsmCall { DeviceState& d; hipStream_t s; const MsmPlan& p; size_t n; bool ordered = false; };
 // region r of the workspace
 template <class T = uint32_t>
 T* msm_at(const MsmCall& c, MsmRegion r) { return reinterpret_cast<T*>(c.d.msm_ws.as<uint8_t>() + c.p.region[r].offset); }
@@ -1632,17 +1691,17 @@ int msm_prepare_count(const MsmCall& c, bool encoded, const void* pts_in, const 
 
 // Phase 2: the scans (bucket offsets, L, the plan of the bucket sums) and the two placement levels of the sort (TileLds: 73 KiB
 // of dynamic LDS each).  Level 1 writes R_TMP_IDX, the view of R_PARTIALS that is free until k_msm_spans.
-template <bool PK, class DT>
+template <bool PK, class DT, bool ORDERED>
 int msm_place(const MsmCall& c) {
   const MsmPlan& p = c.p;
   const size_t tile_lds = sizeof(TileLds);
   uint32_t *tmp_idx = msm_at(c, R_TMP_IDX), *offs = msm_at(c, R_OFFS);
   uint8_t* tmp_sub = msm_at<uint8_t>(c, R_SUB);
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_place1<PK, DT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_place2<PK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
-  hipLaunchKernelGGL((k_msm_place1<PK, DT>), dim3(p.W * p.S), dim3(SORT_THREADS), tile_lds, c.s, msm_at<const DT>(c, R_DIGITS), c.n, p.nb, p.S, p.per,
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_place1<PK, DT, ORDERED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_place2<PK, ORDERED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
+  hipLaunchKernelGGL((k_msm_place1<PK, DT, ORDERED>), dim3(p.W * p.S), dim3(SORT_THREADS), tile_lds, c.s, msm_at<const DT>(c, R_DIGITS), c.n, p.nb, p.S, p.per,
                      msm_at(c, R_BLOCKHIST), offs, tmp_idx, tmp_sub);
-  hipLaunchKernelGGL(k_msm_place2<PK>, dim3(p.W * ((p.nb + SUPER - 1) / SUPER)), dim3(SORT_THREADS), tile_lds, c.s, tmp_idx, tmp_sub, c.n, p.nb, offs,
+  hipLaunchKernelGGL((k_msm_place2<PK, ORDERED>), dim3(p.W * ((p.nb + SUPER - 1) / SUPER)), dim3(SORT_THREADS), tile_lds, c.s, tmp_idx, tmp_sub, c.n, p.nb, offs,
                      msm_at(c, R_IDX));
   return D377_OK;
 }
@@ -1656,8 +1715,12 @@ int msm_scan_place(const MsmCall& c) {
   hipLaunchKernelGGL(k_msm_scan2, grid, dim3(1024), 0, s, offs, bsz, segoff, tot, tot2, p.nb, p.W, p.scan_chunks, p.lanes_target, p.forced_L, p.red,
                      lvlmax, meta);
   hipLaunchKernelGGL(k_msm_scan3, grid, dim3(1024), 0, s, offs, segoff, tot2, p.nb, p.W, p.scan_chunks, meta, msm_at<WinInfo>(c, R_WINFO));
-  if (p.wide_digits) return p.packed ? msm_place<true, int32_t>(c) : msm_place<false, int32_t>(c);
-  return p.packed ? msm_place<true, int16_t>(c) : msm_place<false, int16_t>(c);
+  if (c.ordered) {
+    if (p.wide_digits) return p.packed ? msm_place<true, int32_t, true>(c) : msm_place<false, int32_t, true>(c);
+    return p.packed ? msm_place<true, int16_t, true>(c) : msm_place<false, int16_t, true>(c);
+  }
+  if (p.wide_digits) return p.packed ? msm_place<true, int32_t, false>(c) : msm_place<false, int32_t, false>(c);
+  return p.packed ? msm_place<true, int16_t, false>(c) : msm_place<false, int16_t, false>(c);
 }
 
 // Phase 3: the span sums, the reduction levels and the buckets (msm_bucket_records: R_BUCKETS holds [W][nb] records after it),

@@ -142,7 +142,7 @@ template <class DT, class Map>
 int bsum_pass(DeviceState& d, hipStream_t s, const MsmPlan& p, bool encoded, const void* pts_in, const uint8_t* scalars, const Map& map, size_t K,
               uint8_t* enc_out, uint64_t* xyzt_out, uint8_t* status) {
   const size_t N = map.points(K);
-  const MsmCall call{d, s, p, N};
+  const MsmCall call{d, s, p, N, xyzt_out != nullptr};         // records are returned: their bytes are a function of the inputs
   int rc;
   int16_t* dig = msm_at<int16_t>(call, R_IDX);                  // the plain digits: W N int16 in a region of W N words
   if ((rc = msm_prepare<int16_t>(call, encoded, pts_in, scalars, status, dig))) return rc;

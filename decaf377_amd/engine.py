@@ -537,7 +537,7 @@ class Context:
     # -- Fq on in-memory elements (4 Montgomery u64 limbs) ------------------------------------------
     FQ_OPS = {"add": 0, "sub": 1, "mul": 2, "square": 3, "neg": 4, "inverse": 5}
 
-    def fq_op(self, op, a, b=None):
+    def fq_op(self, op, a, b=None, outs=None):
         """Fq add/sub/mul (binary) and square/neg/inverse (unary) on [n, 4] u64 Montgomery records
         (src/fields/fq/u64/wrapper.rs:99-132) -> (out [n, 4], status [n]); status 1 only for inverse(0).
         numpy arrays (host path) or torch CUDA tensors (device path)."""
@@ -545,45 +545,20 @@ class Context:
         binary = code <= 2
         if binary and b is None:
             raise ValueError("fq_op %s takes two operands" % op)
-        if _is_torch(a):
-            import torch
-            n = _rows(a)
-            dev = a.device
-            di = self._dev_index(dev)
-            _check(a, FQM, n, "fq_op input", dev)
-            if binary:
-                _check(b, FQM, n, "fq_op input", dev)
-            a = a.contiguous()
-            bb = b.contiguous() if binary else None
-            out = torch.empty((n, 4), dtype=torch.int64, device=dev)
-            st = torch.zeros((max(n, 1),), dtype=torch.uint8, device=dev)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _native.check(self._lib.d377_batch_fq_op_dev(self._h, di, stream, code, ctypes.c_void_p(a.data_ptr()),
-                                                         ctypes.c_void_p(bb.data_ptr()) if binary else None,
-                                                         ctypes.c_size_t(n), ctypes.c_void_p(out.data_ptr()),
-                                                         ctypes.c_void_p(st.data_ptr())))
-            return out, st[:n]
-        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
-        n = a.shape[0]
-        out = np.empty((n, 4), np.uint64)
-        st = np.zeros(max(n, 1), np.uint8)
-        p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
-        bb = None
-        if binary:
-            bb = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 4)
-            if bb.shape[0] != n:
-                raise ValueError("fq_op: operands have %d and %d rows" % (n, bb.shape[0]))
-        _native.check(self._lib.d377_batch_fq_op(self._h, code, p(a), p(bb) if bb is not None else None,
-                                                 ctypes.c_size_t(n), p(out), p(st)))
-        return out, st[:n]
+        ins = [a, b] if binary else [a]
+        if not _is_torch(a):                                     # host arrays: any integer layout of n x 4 limbs
+            ins = [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4) for x in ins]
+            if binary and ins[1].shape[0] != ins[0].shape[0]:
+                raise ValueError("fq_op: operands have %d and %d rows" % (ins[0].shape[0], ins[1].shape[0]))
+        return self._run("d377_batch_fq_op", ins, [FQM] * len(ins), [FQM, FLAG], outs, pre=(ctypes.c_int(code),), in_slots=2)
 
-    def fq_from_bytes_checked(self, bytes32):
+    def fq_from_bytes_checked(self, bytes32, outs=None):
         """Fq::from_bytes_checked (src/fields/fq.rs:108-115) -> ([n, 4] u64, status[n])."""
-        return self._run("d377_batch_fq_from_bytes_checked", [bytes32], [ENC], [FQM, FLAG])
+        return self._run("d377_batch_fq_from_bytes_checked", [bytes32], [ENC], [FQM, FLAG], outs)
 
-    def fq_to_bytes(self, a):
+    def fq_to_bytes(self, a, outs=None):
         """Fq::to_bytes_le on [n, 4] u64 Montgomery records -> [n, 32] u8."""
-        return self._run("d377_batch_fq_to_bytes", [a], [FQM], [ENC])[0]
+        return self._run("d377_batch_fq_to_bytes", [a], [FQM], [ENC], outs)[0]
 
     # -- wide byte strings and affine normalisation -----------------------------------------------
     def _wide(self, name, data):

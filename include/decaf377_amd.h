@@ -16,9 +16,14 @@
  *              (failed elements get all-zero output records)
  *
  * Return value: 0 on success, negative D377_ERR_* otherwise; per-element failures are only
- * reported through `status`.  Buffers belong to the caller and are never retained.  An output buffer may
- * be the input buffer of the same record size (in place); until a call completes its output records may hold
- * intermediate values.
+ * reported through `status`.  Buffers belong to the caller and are never retained.  In place: in the element-wise
+ * maps, d377_batch_* and d377_batch_*_dev and through d377_batch_sharded_dev, the output pointer may EQUAL the pointer
+ * of any input whose records have the output's size -- the first input or the second (the scalars of scalar_mul_var,
+ * r2 of hash_to_curve, the denominator of sqrt_ratio_zeta, b of the field operations), or both inputs at once; the status
+ * buffer stays separate.  Until a call completes its output records may hold intermediate values.  Buffers that overlap
+ * without being equal are not supported, and this sentence does not speak for the sums (d377_msm*, d377_batch_*msm*,
+ * d377_sum_elements_dev), whose inputs and outputs differ in count.  Every such map runs in place on every launch route
+ * in tests/test_in_place_gpu.py.
  *
  * Threads and streams.  Calls on one context are serialised by a mutex inside the context, so
  * several host threads may share it; distinct contexts are independent.  The `_dev` entry points

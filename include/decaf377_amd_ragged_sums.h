@@ -24,9 +24,8 @@ extern "C" {
  *   scalar32       offsets[n] scalars, any 32 bytes, reduced mod r.
  *   enc32_out      n Encodings.  An empty sum gives what a sum of dead terms gives: the all-zero Encoding.
  *   xyzt_out       n Element records, or NULL; an empty sum's record is an identity record.
- *                  The records are reproducible only as group elements: two runs on one input may return different
- *                  projective representatives (the sort orders the points of a bucket by atomic counters), as in
- *                  d377_batch_bucket_msm.  enc32_out and status are reproducible byte for byte.
+ *                  The records are reproducible byte for byte, like enc32_out and status: a call that returns records
+ *                  orders the points of a bucket by their position in the input, as d377_batch_bucket_msm does.
  *   window_bits    0: the library's rule, d377_batch_bucket_msm's width for the MEAN length max(1, ceil(offsets[n] / n)).
  *                  4 .. 16 forces the width: a developer and test knob.  Whether the mean is the right statistic for skewed
  *                  lengths is an open item (see the sweep below).

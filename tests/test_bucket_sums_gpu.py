@@ -266,3 +266,32 @@ def test_device_listed_twice_slices_the_sums(oracle):
 
 def test_cpp_mirror_bucket_sums():
     build_and_run_cpp("bucket_sums", "CPP_BUCKET_SUMS_OK", hip_headers=True)
+
+
+# (n, m, window_bits): 2^20 terms each.  12 bits: one pass, 17 super-buckets, 32 points to a bucket; 16 bits: four passes of four
+# sums, 1025 super-buckets (the widest level 1 the sort has), int32 keys; the library's own width.  Every window is 128 tiles of
+# the sort and more, in several slices.
+LARGE = [(16, 1 << 16, 12), (16, 1 << 16, 16), (256, 1 << 12, 0)]
+
+
+@pytest.mark.parametrize("n,m,c", LARGE)
+def test_element_records_are_reproducible_byte_for_byte_at_large_shapes(ctx, torch, n, m, c):
+    """Two runs of one call on one input return the same Element record BYTES, and the ragged call with equal lengths returns
+    them too, where the sort walks many tiles per workgroup, several slices per window and up to 1025 bins: the order of a
+    bucket's points is a function of the inputs (msm.hip tile_scatter, ORDERED).  The sums themselves: every
+    Encoding equals d377_msm's for that sum (another sort order, single-sum keys), and the records compress to them."""
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(7700 + c)
+    pts = ctx.encode_to_curve_element(torch.randint(0, 256, (n * m, 32), dtype=torch.uint8, device=dev, generator=g))
+    k = torch.randint(0, 256, (n * m, 32), dtype=torch.uint8, device=dev, generator=g)
+    k[::1001] = k[0]                                             # one scalar on a thousand points: long runs in one bucket of every window
+    runs = [ctx.msm_buckets(pts, k, m, elements=True, window_bits=c) for _ in range(3)]
+    runs.append(ctx.msm_ragged(pts, k, np.arange(n + 1, dtype=np.uint64) * m, elements=True, window_bits=c))
+    torch.cuda.synchronize()
+    for enc, el in runs[1:]:
+        assert torch.equal(enc, runs[0][0]) and torch.equal(el, runs[0][1]), (n, m, c)
+    enc, el = runs[0]
+    assert torch.equal(ctx.compress(el), enc)
+    for s in (0, n // 2, n - 1):
+        one = ctx.msm(pts[s * m:(s + 1) * m], k[s * m:(s + 1) * m])[0]
+        assert torch.equal(one, enc[s]), (n, m, c, s)

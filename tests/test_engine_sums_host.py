@@ -478,3 +478,52 @@ def test_a_closed_handle_is_refused(ctx, fb):
         with pytest.raises(d.NativeError, match=re.escape("FixedBases: the handle is closed")):
             call()
     assert not ctx._lib.calls
+
+
+# ---- Context.fq_op / fq_from_bytes_checked / fq_to_bytes: outs like every other element-wise map --------------------------------
+def test_fq_maps_take_outs_and_check_them(ctx):
+    n = 3
+    a, b, raw = u64(n, 4), u64(n, 4) + 1, u8(n, 32)
+    # the caller's arrays are the ones the call writes and returns, in place included; the unary codes pass b = NULL
+    out, st = u64(n, 4), u8(n)
+    res = ctx.fq_op("mul", a, b, outs=[out, st])
+    assert res[0] is out and res[1] is st
+    assert last(ctx, "d377_batch_fq_op", 7) == [1, 2, addr(a), addr(b), n, addr(out), addr(st)]
+    res = ctx.fq_op("inverse", a, outs=[a, st])
+    assert res[0] is a and last(ctx, "d377_batch_fq_op", 7) == [1, 5, addr(a), None, n, addr(a), addr(st)]
+    res = ctx.fq_op("add", a, b)
+    shapes(tuple(res), ((n, 4), "u64"), ((n,), "u8"))
+    args = last(ctx, "d377_batch_fq_op", 7)
+    assert args[:5] == [1, 0, addr(a), addr(b), n] and args[5:] == [addr(res[0]), addr(res[1])]
+    res = ctx.fq_from_bytes_checked(raw, outs=[out, st])
+    assert res[0] is out and res[1] is st and last(ctx, "d377_batch_fq_from_bytes_checked", 5) == [1, addr(raw), n, addr(out), addr(st)]
+    shapes(tuple(ctx.fq_from_bytes_checked(raw)), ((n, 4), "u64"), ((n,), "u8"))
+    ctx._lib.calls.clear()
+    enc = u8(n, 32)
+    assert ctx.fq_to_bytes(a, outs=[enc]) is enc and last(ctx, "d377_batch_fq_to_bytes", 4) == [1, addr(a), n, addr(enc)]
+    shapes(ctx.fq_to_bytes(a), ((n, 32), "u8"))
+    ctx._lib.calls.clear()
+    # ... and checked like the inputs, before any call
+    with raises("d377_batch_fq_op: expected 2 output arrays"):
+        ctx.fq_op("mul", a, b, outs=[out])
+    with raises("d377_batch_fq_op output: expected shape (3, 4), got (2, 4)"):
+        ctx.fq_op("mul", a, b, outs=[u64(2, 4), st])
+    with raises("d377_batch_fq_op output: expected shape (3,), got (4,)"):
+        ctx.fq_op("neg", a, outs=[out, u8(4)])
+    with raises("d377_batch_fq_op output: expected uint64/int64 elements, got uint8"):
+        ctx.fq_op("square", a, outs=[u8(n, 4), st])
+    with raises("d377_batch_fq_op output must be contiguous"):
+        ctx.fq_op("mul", a, b, outs=[u64(n, 8)[:, :4], st])
+    with raises("fq_op mul takes two operands"):
+        ctx.fq_op("mul", a, outs=[out, st])
+    with raises("fq_op: operands have 3 and 2 rows"):
+        ctx.fq_op("mul", a, b[:2])
+    with raises("d377_batch_fq_from_bytes_checked output: expected shape (3, 4), got (3, 32)"):
+        ctx.fq_from_bytes_checked(raw, outs=[u8(n, 32), st])
+    with raises("d377_batch_fq_from_bytes_checked: expected 2 output arrays"):
+        ctx.fq_from_bytes_checked(raw, outs=[out])
+    with raises("d377_batch_fq_to_bytes output: expected uint8 elements, got uint64"):
+        ctx.fq_to_bytes(a, outs=[u64(n, 32)])
+    with raises("d377_batch_fq_to_bytes: expected 1 output arrays"):
+        ctx.fq_to_bytes(a, outs=[enc, st])
+    assert not ctx._lib.calls

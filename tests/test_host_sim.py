@@ -27,7 +27,7 @@ def _p(a):
 @pytest.fixture(scope="module")
 def sim():
     lib = os.path.join(SIM_DIR, "libd377_sim.so")
-    srcs = [os.path.join(SIM_DIR, "sim.cpp")] + [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
+    srcs = [os.path.join(SIM_DIR, f) for f in ("sim.cpp", "launch_plan_sim.inc")] + [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
     if not os.path.exists(lib) or any(os.path.getmtime(s) > os.path.getmtime(lib) for s in srcs):
         # -DD377_FB_BITS=12: the product's 23-bit fixed-base comb has 46 M entries, each an inversion -- far too slow to build on a CPU
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-DD377_FB_BITS=12", "-I" + CSRC,
@@ -487,7 +487,7 @@ def test_static_bounds(oracle):
     therefore proves the bounds of every call site.  Runs in a child process: a violation aborts."""
     import sys
     lib = os.path.join(SIM_DIR, "libd377_sim_bounds.so")
-    srcs = [os.path.join(SIM_DIR, "sim.cpp")] + [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
+    srcs = [os.path.join(SIM_DIR, f) for f in ("sim.cpp", "launch_plan_sim.inc")] + [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
     if not os.path.exists(lib) or any(os.path.getmtime(s_) > os.path.getmtime(lib) for s_ in srcs):
         # (-DD377_FB_BITS=8: the small fixed-base comb, so that the unoptimised build's table construction stays short;
         #  the additions it feeds are the same code)

@@ -124,12 +124,10 @@ def test_equal_lengths_give_the_bytes_of_the_bucket_form(ctx, oracle, n, m, c):
 def test_equal_lengths_give_the_element_record_bytes_of_the_bucket_form(ctx, oracle, n, m, c):
     """The Element records of the two calls, byte for byte: the check the feature's specification sets, kept as it sets it.
 
-    It fails at (17, 40, 12) and (16, 40, 12) whenever d377_batch_bucket_msm does not reproduce its own record bytes, which it
-    does not always do: the bytes of an Element record are not a function of the inputs in either call.  On one
-    MI355X the uniform call's record of sum 1 differed between two of its own runs at both shapes, in the same row in which
-    the two calls differed; at (1, 1, 4), (3, 5, 4) and (9, 33, 16) no byte differed in any run.  The records that differ are
-    projective representatives of one group element, and the Encodings and statuses are equal in every run
-    (test_equal_lengths_give_the_bytes_of_the_bucket_form)."""
+    It used to fail at (17, 40, 12) and (16, 40, 12) whenever d377_batch_bucket_msm did not reproduce its own record bytes: the
+    sort ordered the points of a bucket by the arrival of LDS atomics, and the uniform call's record of a sum differed between
+    two of its own runs, in the same row in which the two calls differed.  A call that returns records now sorts in an order that
+    is a function of the inputs (msm.hip tile_scatter, ORDERED), and so are the record bytes of both calls."""
     off = offsets_of([m] * n)
     for encoded in (False, True):
         pts, k, _ = bc.make_case(oracle, np.random.default_rng(100 * n + m + encoded), n, m, c, encoded=encoded)
