@@ -67,6 +67,11 @@ RAGGED_SUMS_EXPORTS = [
     "d377_batch_ragged_msm", "d377_batch_ragged_msm_encoded", "d377_batch_ragged_msm_resident",
     "d377_batch_ragged_msm_encoded_resident", "d377_ragged_msm_plan",
 ]
+# every symbol include/decaf377_amd_segmented_sums.h declares (checked by tests/test_segmented_sums_host.py)
+SEGMENTED_SUMS_EXPORTS = [
+    "d377_batch_segmented_msm", "d377_batch_segmented_msm_encoded", "d377_batch_segmented_msm_resident",
+    "d377_batch_segmented_msm_encoded_resident", "d377_segmented_msm_plan",
+]
 
 
 class CtxOpts(ctypes.Structure):
@@ -265,6 +270,15 @@ def load():
         "d377_batch_ragged_msm_resident": [vp, i32, vp, vp, vp, vp, vp, sz, i32, vp, vp],
         "d377_batch_ragged_msm_encoded_resident": [vp, i32, vp, vp, vp, vp, vp, sz, i32, vp, vp, vp],
         "d377_ragged_msm_plan": [vp, i32, vp, sz, i32, ctypes.POINTER(i32), u64p, u64p, u64p, u64p],
+    })
+    # the same sums by Straus chains (decaf377_amd_segmented_sums.h): host forms, resident forms, the plan
+    i32p = ctypes.POINTER(i32)
+    resident.update({
+        "d377_batch_segmented_msm": [vp, vp, vp, vp, sz, vp, vp],
+        "d377_batch_segmented_msm_encoded": [vp, vp, vp, vp, sz, vp, vp, vp],
+        "d377_batch_segmented_msm_resident": [vp, i32, vp, vp, vp, vp, vp, sz, vp, vp],
+        "d377_batch_segmented_msm_encoded_resident": [vp, i32, vp, vp, vp, vp, vp, sz, vp, vp, vp],
+        "d377_segmented_msm_plan": [vp, i32, vp, sz, u64p, u64p, i32p, i32p, u64p, i32p],
     })
     for name, args in resident.items():
         getattr(lib, name).argtypes = args

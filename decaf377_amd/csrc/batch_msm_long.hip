@@ -154,6 +154,16 @@ int long_sums_partials(DeviceState& d, hipStream_t s, size_t n, size_t g, uint64
   return D377_OK;
 }
 
+int long_sums_partials_records(DeviceState& d, hipStream_t s, size_t records, size_t tail_bytes, uint64_t** partials) {
+  *partials = nullptr;
+  int rc;
+  if ((rc = d.bml_partials.reserve(d.vb_guard, s, records * 128 + tail_bytes, SLACK_PARTIALS,
+         "batch_segmented_msm: the partial sums' area must grow, which cannot happen inside a stream capture",
+         "batch_segmented_msm: hipMalloc of the partial sums' area failed (%zu bytes: 128 bytes per slot of a chain or a fold level)"))) return rc;
+  *partials = d.bml_partials.as<uint64_t>();
+  return D377_OK;
+}
+
 int long_sums_fold_compress(DeviceState& d, hipStream_t s, size_t n, size_t g, uint8_t* out32, uint64_t* xyzt_out) {
   uint64_t* partials = d.bml_partials.as<uint64_t>();
   const size_t np = n * g;

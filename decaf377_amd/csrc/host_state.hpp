@@ -37,6 +37,7 @@ struct DeviceState : PlanDev {               // (launch_plan.hpp: the CU count a
   int dcb_sets = 0;                      // lane sets of the round-record area and its pool (the largest chunk_sets x CUs)
   int bm_lds[2] = {-1, -1};              // batch_msm.hip: LDS padding of its lane kernel (Element / Encoding form), -1 = not asked yet
   int bml_lds[2] = {-1, -1};             // batch_msm_long.hip: LDS padding of its lane kernel (Element / Encoding form), -1 = not asked yet
+  int seg_lds[2] = {-1, -1};             // batch_msm_segmented.hip: the same for its lane kernel
   int bmli_lds = -1;                     // batch_msm_long_indexed.hip: LDS padding of its lane kernel, -1 = not asked yet
   uint8_t* bmli_pool = nullptr;          // batch_msm_long_indexed.hip: the pool's staging area of the host form; grown on demand
   size_t bmli_pool_cap = 0;

@@ -12,6 +12,9 @@ namespace d377 {
 // n g partial sums go to its start, sum-major (record s g + q).  The area may not grow inside a stream capture (D377_ERR_ARG).
 // The caller holds ctx->mu and the scope of the lane-set guard (GuardScope on d.vb_guard), not yet acquired.
 int long_sums_partials(DeviceState& d, hipStream_t s, size_t n, size_t g, uint64_t** partials);
+// The same area sized by its caller (batch_msm_segmented.hip: the slot spaces of its levels, its compact records and, behind
+// them, the offsets a host form uploads): room for `records` records and `tail_bytes` more.  The same rules.
+int long_sums_partials_records(DeviceState& d, hipStream_t s, size_t records, size_t tail_bytes, uint64_t** partials);
 // Folds the n x g partial sums at the start of the partials area (g > 1) until one record per sum is left -- the last level
 // writes into xyzt_out when that is not null -- and compresses the n sums into out32 in chunks with batched inversions
 // (codec_chunked.hip; the caller has asked codec_chunked_ok).  Enqueued on `s`; the caller holds the acquired guard scope.

@@ -756,6 +756,70 @@ class Context:
         return {"window_bits": c.value, "passes": v[0].value, "max_sums_per_pass": v[1].value, "max_points_per_pass": v[2].value,
                 "workspace_bytes": v[3].value}
 
+    def msm_segmented(self, points, scalar32, offsets, outs=None, elements=False, offsets_dev=None):
+        """n independent multiscalar sums of ANY length each, 0 .. 2^20 terms per sum, by Straus chains
+        (d377_batch_segmented_msm[_encoded], include/decaf377_amd_segmented_sums.h): msm_ragged's arguments without
+        window_bits, its Encodings and statuses byte for byte, and msm_long's cut of every sum into chains of at most 8 terms
+        -- the call for MANY SHORT sums of unequal length (msm_segmented_plan's "advised_route", which msm_by_offsets
+        follows).  Element records are some representative of the sums, not msm_ragged's bytes.  Routing is msm_ragged's:
+        tensors on a device of the context take the resident form on torch's current stream (one eager call of a shape
+        before capturing it in a graph).  offsets_dev: the same n + 1 values as a uint64 / int64 tensor on that device, which
+        the kernels read.  When it is None THIS METHOD ALLOCATES A TENSOR AND COPIES THE OFFSETS TO THE DEVICE, which a
+        stream capture does not allow: a caller who captures a graph passes its own.  Nothing checks that offsets_dev holds
+        the values of offsets; if it does not, the sums are wrong (memory stays safe)."""
+        what = "msm_segmented"
+        off = self._offsets(what, offsets)
+        n = int(off.size) - 1
+        if points.ndim != 2 or int(points.shape[1]) not in (16, 32):
+            raise ValueError(what + ": points must be [terms, 16] Elements or [terms, 32] Encodings")
+        encoded, terms = int(points.shape[1]) == 32, _rows(points)
+        if terms != int(off[n]):
+            raise ValueError(what + ": offsets[n] = %d, but there are %d points" % (int(off[n]), terms))
+        held = []                                                # keeps the uploaded offsets alive through the call
+
+        def mid(dev):
+            args = [_ptr(off)]
+            if dev is not None:
+                od = offsets_dev
+                if od is None:
+                    od = _on_device(dev, off)
+                elif not (_is_torch(od) and od.device == dev and od.dtype in _u64_dtypes() and tuple(od.shape) == (n + 1,)
+                          and od.is_contiguous()):
+                    raise ValueError(what + ": offsets_dev must be a contiguous [n + 1] uint64/int64 tensor on the points' device")
+                held.append(od)
+                args.append(_ptr(od))
+            return (*args, ctypes.c_size_t(n))
+
+        return self._sums(what, ("d377_batch_segmented_msm", "d377_batch_segmented_msm_encoded"),
+                          ("d377_batch_segmented_msm_resident", "d377_batch_segmented_msm_encoded_resident"), points, scalar32, encoded, terms,
+                          n, outs, elements, mid)
+
+    def msm_segmented_plan(self, offsets, dev=0):
+        """The plan of msm_segmented for the sums `offsets` delimits on device `dev` of the context (d377_segmented_msm_plan)
+        -> {"chain_slots", "chains", "fold_levels", "max_slots_per_chain", "scratch_bytes", "advised_route"}; advised_route
+        is "chains" (this call) or "buckets" (msm_ragged)."""
+        off = self._offsets("msm_segmented_plan", offsets)
+        u = [ctypes.c_uint64(0) for _ in range(3)]
+        c = [ctypes.c_int(0) for _ in range(3)]
+        _native.check(self._lib.d377_segmented_msm_plan(self._h, int(dev), _ptr(off), ctypes.c_size_t(int(off.size) - 1), ctypes.byref(u[0]),
+                                                        ctypes.byref(u[1]), ctypes.byref(c[0]), ctypes.byref(c[1]), ctypes.byref(u[2]),
+                                                        ctypes.byref(c[2])))
+        return {"chain_slots": u[0].value, "chains": u[1].value, "fold_levels": c[0].value, "max_slots_per_chain": c[1].value,
+                "scratch_bytes": u[2].value, "advised_route": ("chains", "buckets")[c[2].value]}
+
+    def msm_by_offsets(self, points, scalar32, offsets, outs=None, elements=False, offsets_dev=None, route="auto"):
+        """n sums delimited by offsets on the route that suits their lengths: the whole call goes to msm_segmented
+        (route="chains") or to msm_ragged with the library's window rule (route="buckets"); "auto" takes
+        msm_segmented_plan's advised_route for the device the points live on (device 0 of the context for host arrays).
+        The Encodings and statuses do not depend on the route; Element records are some representative of the same sums."""
+        if route not in ("auto", "chains", "buckets"):
+            raise ValueError('msm_by_offsets: route must be "auto", "chains" or "buckets"')
+        if route == "auto":
+            dev = _cuda_device(self, points) if _is_torch(points) else None
+            route = self.msm_segmented_plan(offsets, dev=self._dev_index(dev) if dev is not None else 0)["advised_route"]
+        call = self.msm_segmented if route == "chains" else self.msm_ragged
+        return call(points, scalar32, offsets, outs=outs, elements=elements, offsets_dev=offsets_dev)
+
     def msm_long_indexed(self, pool, point_index, scalar32, m, elements=False, check_indices=True, outs=None):
         """n sums of m terms that name their points in a shared pool (d377_batch_long_msm_indexed):
 

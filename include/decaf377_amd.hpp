@@ -618,6 +618,30 @@ class Engine {
                                                  offsets, offsets_dev, n, window_bits, reinterpret_cast<uint8_t*>(enc_out),
                                                  reinterpret_cast<uint64_t*>(elements_out), status));
   }
+  /// The same sums by Straus chains (d377_batch_segmented_msm, decaf377_amd_segmented_sums.h): every sum cut into chains of at
+  /// most 8 terms, as vartime_multiscalar_mul_batch_long cuts sums of one length -- the call for MANY SHORT sums of unequal
+  /// length.  The Encodings are vartime_multiscalar_mul_batch_ragged's; the Elements are some representative of the same sums.
+  std::vector<Element> vartime_multiscalar_mul_batch_segmented(const std::vector<uint64_t>& offsets, const std::vector<Fr>& scalars,
+                                                               const std::vector<Element>& points, std::vector<Encoding>* encodings = nullptr) {
+    if (scalars.size() != points.size() || offsets.empty() || offsets.back() != points.size()) throw std::invalid_argument("length mismatch");
+    std::vector<Element> out(offsets.size() - 1);
+    std::vector<Encoding> enc(out.size());
+    check(d377_batch_segmented_msm(ctx_, u64(points), u8(scalars), offsets.data(), out.size(), u8m(enc), reinterpret_cast<uint64_t*>(out.data())));
+    if (encodings) *encodings = std::move(enc);
+    return out;
+  }
+  /// ... on DEVICE pointers: msm_ragged_resident's contract without window_bits.  The kernels read `offsets_dev` alone.
+  void msm_segmented_resident(int dev, void* stream, const Element* points, const Fr* scalars, const uint64_t* offsets,
+                              const uint64_t* offsets_dev, size_t n, Encoding* enc_out, Element* elements_out = nullptr) {
+    check(d377_batch_segmented_msm_resident(ctx_, dev, stream, reinterpret_cast<const uint64_t*>(points), reinterpret_cast<const uint8_t*>(scalars),
+                                            offsets, offsets_dev, n, reinterpret_cast<uint8_t*>(enc_out), reinterpret_cast<uint64_t*>(elements_out)));
+  }
+  void msm_segmented_resident(int dev, void* stream, const Encoding* points, const Fr* scalars, const uint64_t* offsets,
+                              const uint64_t* offsets_dev, size_t n, Encoding* enc_out, Element* elements_out, uint8_t* status) {
+    check(d377_batch_segmented_msm_encoded_resident(ctx_, dev, stream, reinterpret_cast<const uint8_t*>(points),
+                                                    reinterpret_cast<const uint8_t*>(scalars), offsets, offsets_dev, n,
+                                                    reinterpret_cast<uint8_t*>(enc_out), reinterpret_cast<uint64_t*>(elements_out), status));
+  }
   /// CurveGroup::normalize_batch (src/ark_curve/element.rs:74-81): affine (x, y) as 4 Montgomery limbs each
   std::vector<std::array<uint64_t, 8>> normalize_batch(const std::vector<Element>& p) {
     std::vector<std::array<uint64_t, 8>> out(p.size());

@@ -54,8 +54,9 @@ extern "C" {
  *
  * WHICH CALL WHERE.  This call has no short-sum route: every (window, sum) pair costs a workgroup of the tree of bit-sums and
  * every sum 2^(window-1) buckets of workspace, whatever its length.  When most sums are below about 1000 terms (the crossover
- * measured for equal lengths in decaf377_amd_bucket_sums.h), pad to the longest sum and use d377_batch_long_msm_indexed with
- * -1 for the absent terms instead.  One sum is d377_msm.  Equal lengths are d377_batch_bucket_msm (no offsets to keep in two
+ * measured for equal lengths in decaf377_amd_bucket_sums.h), use d377_batch_segmented_msm (decaf377_amd_segmented_sums.h)
+ * instead: the same arguments without window_bits, the same Encodings and statuses, by Straus chains;
+ * d377_segmented_msm_plan's advised_route makes the choice.  One sum is d377_msm.  Equal lengths are d377_batch_bucket_msm (no offsets to keep in two
  * places).
  * Measured on one MI355X, device buffers, the legs alternating in one process, median of 5 after 2 warm-ups with each leg's
  * min-to-max spread, timed to the end of a device synchronise, the legs' Encodings compared

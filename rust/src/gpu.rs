@@ -42,6 +42,8 @@ pub mod ffi_long_sums;                                            // rust/src/ff
 pub mod ffi_bucket_sums;                                          // rust/src/ffi_bucket_sums.rs, from include/decaf377_amd_bucket_sums.h
 #[path = "gpu/ffi_ragged_sums.rs"]
 pub mod ffi_ragged_sums;                                          // rust/src/ffi_ragged_sums.rs, from include/decaf377_amd_ragged_sums.h
+#[path = "gpu/ffi_segmented_sums.rs"]
+pub mod ffi_segmented_sums;                                       // rust/src/ffi_segmented_sums.rs, from include/decaf377_amd_segmented_sums.h
 
 /// Which backend's root `sqrt_ratio_zeta_batch` returns (the flags are the same).
 #[derive(Copy, Clone, Debug, PartialEq, Eq)]
@@ -591,6 +593,26 @@ impl Element {
         })?;
         Ok((out.chunks_exact(16).map(element_from_xyzt).collect(), enc))
     }
+    /// The same sums by Straus chains (d377_batch_segmented_msm): every sum cut into chains of at most 8 terms, as
+    /// `vartime_multiscalar_mul_batch_long_gpu` cuts sums of one length.  The call for MANY SHORT sums of unequal length; the
+    /// Encodings are those of `vartime_multiscalar_mul_batch_ragged_gpu`, the Elements some representative of the same sums.
+    pub fn vartime_multiscalar_mul_batch_segmented_gpu(ctx: &GpuContext, offsets: &[usize], scalars: &[Fr], points: &[Element])
+        -> Result<(Vec<Element>, Vec<Encoding>), GpuError> {
+        assert_eq!(scalars.len(), points.len());
+        assert!(!offsets.is_empty() && offsets[0] == 0 && offsets[offsets.len() - 1] == points.len());
+        assert!(offsets.windows(2).all(|w| w[0] <= w[1]));
+        let n = offsets.len() - 1;
+        let off: Vec<u64> = offsets.iter().map(|&o| o as u64).collect();
+        let xyzt = elements_to_xyzt(points);
+        let bytes = pack32(scalars, |k| k.to_bytes());
+        let mut enc = vec![Encoding([0u8; 32]); n];
+        let mut out = vec![0u64; 16 * n];
+        check(unsafe {
+            ffi_segmented_sums::d377_batch_segmented_msm(ctx.0, xyzt.as_ptr(), bytes.as_ptr(), off.as_ptr(), n, enc.as_mut_ptr() as *mut u8,
+                                                         out.as_mut_ptr())
+        })?;
+        Ok((out.chunks_exact(16).map(element_from_xyzt).collect(), enc))
+    }
     /// Long sums whose terms name their points: sum i = sum over j < m of scalars[i m + j] * pool[point_index[i m + j]]
     /// (d377_batch_long_msm_indexed).  -1 is an absent term; any other index outside the pool is refused before any launch.
     pub fn vartime_multiscalar_mul_batch_long_indexed_gpu(ctx: &GpuContext, m: usize, pool: &[Element], point_index: &[i32], scalars: &[Fr])
@@ -852,5 +874,22 @@ pub mod dev {
         assert!(!offsets.is_empty());
         check(ffi_ragged_sums::d377_batch_ragged_msm_encoded_resident(ctx.0, dev, stream, enc32, scalar32, offsets.as_ptr(), offsets_dev,
                                                                       offsets.len() - 1, window_bits, enc32_out, xyzt_out, status))
+    }
+
+    // The same sums by Straus chains on device buffers (ffi_segmented_sums.rs): msm_ragged_resident's contract without
+    // window_bits.  The kernels read `offsets_dev` alone; a mismatch with `offsets` gives wrong sums and safe memory.
+    pub unsafe fn msm_segmented_resident(ctx: &GpuContext, dev: i32, stream: *mut c_void, xyzt: *const u64, scalar32: *const u8,
+                                         offsets: &[u64], offsets_dev: *const u64, enc32_out: *mut u8, xyzt_out: *mut u64)
+        -> Result<(), GpuError> {
+        assert!(!offsets.is_empty());
+        check(ffi_segmented_sums::d377_batch_segmented_msm_resident(ctx.0, dev, stream, xyzt, scalar32, offsets.as_ptr(), offsets_dev,
+                                                                    offsets.len() - 1, enc32_out, xyzt_out))
+    }
+    pub unsafe fn msm_segmented_encoded_resident(ctx: &GpuContext, dev: i32, stream: *mut c_void, enc32: *const u8, scalar32: *const u8,
+                                                 offsets: &[u64], offsets_dev: *const u64, enc32_out: *mut u8, xyzt_out: *mut u64,
+                                                 status: *mut u8) -> Result<(), GpuError> {
+        assert!(!offsets.is_empty());
+        check(ffi_segmented_sums::d377_batch_segmented_msm_encoded_resident(ctx.0, dev, stream, enc32, scalar32, offsets.as_ptr(),
+                                                                            offsets_dev, offsets.len() - 1, enc32_out, xyzt_out, status))
     }
 }
