@@ -26,7 +26,7 @@ VARIANT ?=
 
 CSRC := decaf377_amd/csrc
 LIBDIR := decaf377_amd/lib
-HDRS := $(wildcard $(CSRC)/*.hpp) $(wildcard $(CSRC)/*.inc) include/decaf377_amd.h include/decaf377_amd_resident.h include/decaf377_amd_long_sums.h include/decaf377_amd_bucket_sums.h include/decaf377_amd_ragged_sums.h include/decaf377_amd_segmented_sums.h
+HDRS := $(wildcard $(CSRC)/*.hpp) $(wildcard $(CSRC)/*.inc) include/decaf377_amd.h include/decaf377_amd_resident.h include/decaf377_amd_long_sums.h include/decaf377_amd_bucket_sums.h include/decaf377_amd_ragged_sums.h include/decaf377_amd_segmented_sums.h include/decaf377_amd_short_msm.h
 UNITS := d377 msm codec_chunked batch_msm batch_msm_long batch_msm_long_indexed fixed_bases batch_msm_mixed batch_msm_segmented
 DEFS := -DD377_FB_BITS=$(FB_BITS) -DD377_DCB_K=$(DCB_K) -DD377_WAVES_PER_SIMD=$(WAVES_PER_SIMD) $(EXTRA)
 ifeq ($(CHECK_INVARIANTS),1)

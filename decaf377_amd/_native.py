@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI declared in include/decaf377_amd.h (and decaf377_amd_resident.h, decaf377_amd_long_sums.h and
-decaf377_amd_bucket_sums.h, which it includes).
+decaf377_amd_bucket_sums.h and the other headers it includes).
 
 The shared library is built in-tree by `__graft_entry__.build()` (hipcc, gfx950) as
 decaf377_amd/lib/libdecaf377_amd.so.  There is no CPU fallback: if the library is missing
@@ -71,6 +71,10 @@ RAGGED_SUMS_EXPORTS = [
 SEGMENTED_SUMS_EXPORTS = [
     "d377_batch_segmented_msm", "d377_batch_segmented_msm_encoded", "d377_batch_segmented_msm_resident",
     "d377_batch_segmented_msm_encoded_resident", "d377_segmented_msm_plan",
+]
+# every symbol include/decaf377_amd_short_msm.h declares (checked by tests/test_msm_short_host.py)
+SHORT_MSM_EXPORTS = [
+    "d377_msm_short", "d377_msm_short_encoded", "d377_msm_short_dev", "d377_msm_short_encoded_dev", "d377_msm_short_plan",
 ]
 
 
@@ -279,6 +283,14 @@ def load():
         "d377_batch_segmented_msm_resident": [vp, i32, vp, vp, vp, vp, vp, sz, vp, vp],
         "d377_batch_segmented_msm_encoded_resident": [vp, i32, vp, vp, vp, vp, vp, sz, vp, vp, vp],
         "d377_segmented_msm_plan": [vp, i32, vp, sz, u64p, u64p, i32p, i32p, u64p, i32p],
+    })
+    # the one long sum over 8- and 16-byte scalars (decaf377_amd_short_msm.h): host forms, _dev forms, the plan
+    resident.update({
+        "d377_msm_short": [vp, vp, vp, i32, sz, vp, vp],
+        "d377_msm_short_encoded": [vp, vp, vp, i32, sz, vp, vp, vp],
+        "d377_msm_short_dev": [vp, i32, vp, vp, vp, i32, sz, vp, vp],
+        "d377_msm_short_encoded_dev": [vp, i32, vp, vp, vp, i32, sz, vp, vp, vp],
+        "d377_msm_short_plan": [vp, i32, sz, i32, i32p, i32p, u64p],
     })
     for name, args in resident.items():
         getattr(lib, name).argtypes = args

@@ -24,6 +24,10 @@
 //   k_msm_final     Horner over the windows (c doublings per window) on four lanes per point (quad_ops.hpp), the encoding
 //   k_msm_small(_sum)  batches of up to 4 x 16 x CUs points skip all of the above: one quad of lanes per point, see there
 //
+// d377_msm_short (8- and 16-byte scalars: decaf377_amd_short_msm.h) is the same pipeline on the digits of k itself, over the
+// fewer windows that tile 8 * bytes + 1 bits: k_msm_short_prepare_* read the narrow records, everything from the sort to the
+// tree runs unchanged on ws.W windows, and k_msm_final<false> encodes the sum with a square root instead of doubling a half.
+//
 // Group-element outputs are canonical as encodings, so the result bytes equal the reference's
 // whatever the summation order (the scatter order is non-deterministic; the sum is not).
 //
@@ -93,12 +97,46 @@ __device__ __forceinline__ void msm_write_digits(const uint8_t* scalar32, size_t
     digits[(size_t)w * n + i] = (DT)d;
   }
 }
+// d377_msm_short's scalars: packed records of 8 or 16 bytes, each a scalar below 2^128 < r as it stands.  One load, the value
+// zero-extended to the eight words msm_digit reads, no reduction and no halving: the digits are those of k itself, over the
+// windows that tile 8 * bytes + 1 bits (msm_plan.hpp: win_shape_bits), and the sum is not doubled at the end (k_msm_final<false>).
+template <class DT>
+__device__ __forceinline__ void msm_write_digits_short(const uint8_t* scalars, int bytes, size_t i, size_t n, const WinShape& ws, bool skip, DT* digits) {
+  uint32_t k[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (bytes == 16) {
+    const uint4 v = reinterpret_cast<const uint4*>(scalars)[i];
+    k[0] = v.x; k[1] = v.y; k[2] = v.z; k[3] = v.w;
+  } else {
+    const uint2 v = reinterpret_cast<const uint2*>(scalars)[i];
+    k[0] = v.x; k[1] = v.y;
+  }
+  uint32_t carry = 0;
+#pragma unroll 1
+  for (int w = 0; w < ws.W; ++w) {
+    int d = msm_digit(k, w, ws, carry);
+    if (skip) d = 0;
+    digits[(size_t)w * n + i] = (DT)d;
+  }
+}
+// The scalars of a prepare kernel: where they lie and how a point's digits are read from them.  The four prepare kernels' bodies
+// take either; the kernels of the 32-byte form keep their names and arguments (tests/test_codegen.py guards k_msm_prepare_affine).
+struct ScalarsFr {
+  const uint8_t* p;
+  template <class DT>
+  __device__ __forceinline__ void write_digits(size_t i, size_t n, const WinShape& ws, bool skip, DT* digits) const { msm_write_digits(p, i, n, ws, skip, digits); }
+};
+struct ScalarsShort {
+  const uint8_t* p; int bytes;
+  template <class DT>
+  __device__ __forceinline__ void write_digits(size_t i, size_t n, const WinShape& ws, bool skip, DT* digits) const {
+    msm_write_digits_short(p, bytes, i, n, ws, skip, digits);
+  }
+};
 
 // Encodings: one lane per point; decompression leaves Z = 1, so the affine record costs nothing extra.
-template <class DT>
-__global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD)
-k_msm_prepare_enc(SqrtTables T, const uint8_t* enc32, const uint8_t* scalar32, size_t n, WinShape ws,
-                  uint32_t* pts, DT* digits, uint8_t* status) {
+template <class DT, class SC>
+__device__ __forceinline__ void msm_prepare_enc_body(SqrtTables T, const uint8_t* enc32, const SC sc, size_t n, const WinShape& ws,
+                                                     uint32_t* pts, DT* digits, uint8_t* status) {
   D377_POW_LDS();
   for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (size_t)gridDim.x * BLOCK) {
     uint32_t w[8];
@@ -108,18 +146,28 @@ k_msm_prepare_enc(SqrtTables T, const uint8_t* enc32, const uint8_t* scalar32, s
     status[i] = (uint8_t)bad;
     const fe x = fe_select(bad != 0, fe_zero(), g.x), y = fe_select(bad != 0, fe_const(FE_ONE), g.y);
     pt_store_affine(pts + i * AP_WORDS, gea_from_affine(x, y));
-    msm_write_digits(scalar32, i, n, ws, bad != 0, digits);
+    sc.write_digits(i, n, ws, bad != 0, digits);
   }
+}
+template <class DT>
+__global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD)
+k_msm_prepare_enc(SqrtTables T, const uint8_t* enc32, const uint8_t* scalar32, size_t n, WinShape ws,
+                  uint32_t* pts, DT* digits, uint8_t* status) {
+  msm_prepare_enc_body(T, enc32, ScalarsFr{scalar32}, n, ws, pts, digits, status);
+}
+template <class DT>
+__global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD)
+k_msm_short_prepare_enc(SqrtTables T, const uint8_t* enc32, ScalarsShort sc, size_t n, WinShape ws, uint32_t* pts, DT* digits, uint8_t* status) {
+  msm_prepare_enc_body(T, enc32, sc, n, ws, pts, digits, status);
 }
 
 // The same in chunks with the square roots' denominators inverted together (dcb.hpp; as k_scalar_mul_var and
 // k_decompress_chunked decode their points): 5-8 % fewer cycles per decompression; msm_launch uses it from DCB_ASSIST_MIN
 // points per resident lane, like d377_batch_decompress (393 216 points on 256 CUs: the call -0.7 % there, -2 % at 2^20, -4 % at
 // 2^22; profiles/r05_decompress_route_sweep.txt).
-template <class DT>
-__global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD)
-k_msm_prepare_enc_chunked(SqrtTables T, const uint8_t* enc32, const uint8_t* scalar32, size_t n, WinShape ws,
-                          uint32_t* pts, DT* digits, uint8_t* status, DcbScratch dcb) {
+template <class DT, class SC>
+__device__ __forceinline__ void msm_prepare_enc_chunked_body(SqrtTables T, const uint8_t* enc32, const SC sc, size_t n, const WinShape& ws,
+                                                             uint32_t* pts, DT* digits, uint8_t* status, const DcbScratch& dcb) {
   D377_POW_LDS();
   D377_DCB_BEGIN(status);
   dcb_rounds<1, false, false>(n, io, pt,
@@ -137,9 +185,21 @@ k_msm_prepare_enc_chunked(SqrtTables T, const uint8_t* enc32, const uint8_t* sca
       status[i] = (uint8_t)bad;
       const fe x = fe_select(bad != 0, fe_zero(), g.x), y = fe_select(bad != 0, fe_const(FE_ONE), g.y);
       pt_store_affine(pts + i * AP_WORDS, gea_from_affine(x, y));
-      msm_write_digits(scalar32, i, n, ws, bad != 0, digits);
+      sc.write_digits(i, n, ws, bad != 0, digits);
     });
   D377_DCB_END();
+}
+template <class DT>
+__global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD)
+k_msm_prepare_enc_chunked(SqrtTables T, const uint8_t* enc32, const uint8_t* scalar32, size_t n, WinShape ws,
+                          uint32_t* pts, DT* digits, uint8_t* status, DcbScratch dcb) {
+  msm_prepare_enc_chunked_body(T, enc32, ScalarsFr{scalar32}, n, ws, pts, digits, status, dcb);
+}
+template <class DT>
+__global__ void __launch_bounds__(BLOCK, WAVES_PER_SIMD)
+k_msm_short_prepare_enc_chunked(SqrtTables T, const uint8_t* enc32, ScalarsShort sc, size_t n, WinShape ws, uint32_t* pts, DT* digits, uint8_t* status,
+                                DcbScratch dcb) {
+  msm_prepare_enc_chunked_body(T, enc32, sc, n, ws, pts, digits, status, dcb);
 }
 
 // Elements.  Decompression output and affine inputs have Z = 1 (the record's words are those of 1 * 2^256 mod q); then
@@ -152,10 +212,9 @@ k_msm_prepare_enc_chunked(SqrtTables T, const uint8_t* enc32, const uint8_t* sca
 // 128-byte Element and stores its own 128-byte affine record issues 6 + 8 instructions that each touch 64 lines and use an
 // eighth of them; a wave moves its 64 records as eight coalesced 1 KiB instructions each way instead (HBM-priced kernel: 320
 // bytes per point).
-template <class DT>
-__global__ void __launch_bounds__(BLOCK, 4)
-k_msm_prepare_affine(SqrtTables T, const uint64_t* xyzt, const uint8_t* scalar32, size_t n, WinShape ws, uint32_t* pts, DT* digits,
-                     uint32_t* flag) {
+template <class DT, class SC>
+__device__ __forceinline__ void msm_prepare_affine_body(SqrtTables T, const uint64_t* xyzt, const SC sc, size_t n, const WinShape& ws, uint32_t* pts,
+                                                        DT* digits, uint32_t* flag) {
   (void)T;
   D377_RECORD_TILES(rec0) {
     // Once any wave has met a Z != 1, k_msm_prepare_el redoes the whole batch and nothing written here is used: the wave
@@ -189,18 +248,28 @@ k_msm_prepare_affine(SqrtTables T, const uint64_t* xyzt, const uint8_t* scalar32
 #pragma unroll
     for (int k = 3 * NL; k < AP_WORDS; ++k) w[k] = 0;
     wave_store_records128(reinterpret_cast<uint64_t*>(pts), rec0, n, tile, lane, w);
-    if (live) msm_write_digits(scalar32, i, n, ws, false, digits);
+    if (live) sc.write_digits(i, n, ws, false, digits);
   }
+}
+template <class DT>
+__global__ void __launch_bounds__(BLOCK, 4)
+k_msm_prepare_affine(SqrtTables T, const uint64_t* xyzt, const uint8_t* scalar32, size_t n, WinShape ws, uint32_t* pts, DT* digits,
+                     uint32_t* flag) {
+  msm_prepare_affine_body(T, xyzt, ScalarsFr{scalar32}, n, ws, pts, digits, flag);
+}
+template <class DT>
+__global__ void __launch_bounds__(BLOCK, 4)
+k_msm_short_prepare_affine(SqrtTables T, const uint64_t* xyzt, ScalarsShort sc, size_t n, WinShape ws, uint32_t* pts, DT* digits, uint32_t* flag) {
+  msm_prepare_affine_body(T, xyzt, sc, n, ws, pts, digits, flag);
 }
 
 // Elements with some Z != 1: Montgomery's trick per lane, as in k_to_affine -- forward pass multiplies the z's of the
 // lane's grid-stride elements up, parking each prefix product in the element's own record slot; one inversion;
 // the backward pass peels 1/z_i off, writes the affine record and the digits.  A record with z = 0 is no group
 // element: it becomes the identity with digits 0.
-template <class DT>
-__global__ void __launch_bounds__(BLOCK, 4)
-k_msm_prepare_el(const uint64_t* xyzt, const uint8_t* scalar32, size_t n, WinShape ws, uint32_t* pts, DT* digits,
-                 const uint32_t* flag) {
+template <class DT, class SC>
+__device__ __forceinline__ void msm_prepare_el_body(const uint64_t* xyzt, const SC sc, size_t n, const WinShape& ws, uint32_t* pts, DT* digits,
+                                                    const uint32_t* flag) {
   if (*flag == 0) return;
   const size_t Tn = (size_t)gridDim.x * BLOCK, t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
   const bool live = t < n;                               // (a lane without points still takes part in the wave's inversion)
@@ -236,9 +305,20 @@ k_msm_prepare_el(const uint64_t* xyzt, const uint8_t* scalar32, size_t n, WinSha
     x = fe_select(zz, fe_zero(), x);
     y = fe_select(zz, fe_const(FE_ONE), y);
     pt_store_affine(pts + i * AP_WORDS, gea_from_affine(x, y));
-    msm_write_digits(scalar32, i, n, ws, zz, digits);
+    sc.write_digits(i, n, ws, zz, digits);
     if (i == t) break;
   }
+}
+template <class DT>
+__global__ void __launch_bounds__(BLOCK, 4)
+k_msm_prepare_el(const uint64_t* xyzt, const uint8_t* scalar32, size_t n, WinShape ws, uint32_t* pts, DT* digits,
+                 const uint32_t* flag) {
+  msm_prepare_el_body(xyzt, ScalarsFr{scalar32}, n, ws, pts, digits, flag);
+}
+template <class DT>
+__global__ void __launch_bounds__(BLOCK, 4)
+k_msm_short_prepare_el(const uint64_t* xyzt, ScalarsShort sc, size_t n, WinShape ws, uint32_t* pts, DT* digits, const uint32_t* flag) {
+  msm_prepare_el_body(xyzt, sc, n, ws, pts, digits, flag);
 }
 
 // Counting sort of the points of every window by |digit|.  The histogram of a whole window (nb <= 2^13 + 1
@@ -1320,7 +1400,14 @@ __device__ __forceinline__ void msm_emit_doubled(const ge& r, bool first, uint8_
   }
 }
 
-// Horner over the window sums S_w (lanes 0-3 of one wave), result as Element record and as encoding
+// Horner over the window sums S_w (lanes 0-3 of one wave), result as Element record and as encoding.
+// HALVED (d377_msm): the digits were those of k / 2 mod r, the result is the double of the chain's.  Not HALVED (d377_msm_short:
+// the digits of k itself): the chain's result R is the sum, a general point whose Encoding needs the square root.  Its power
+// chains (~300 products) run in the lane-spread form on the wave that is here anyway (row::row_sqrt_powers, as k_msm_tiny
+// decompresses), the table phase and the rest of the compressor on lane 0: 126 us of this kernel behind the Horner chain,
+// against the 184 us of the one-lane compressor (k_msm_combine with m = 1 on the record, the first form of this; kernel
+// traces at 2^20).
+template <bool HALVED>
 __global__ void __launch_bounds__(64, 1)
 k_msm_final(SqrtTables T, const uint32_t* sums, WinShape ws, uint8_t* enc_out, uint64_t* xyzt_out) {
   const int W = ws.W;
@@ -1351,7 +1438,30 @@ k_msm_final(SqrtTables T, const uint32_t* sums, WinShape ws, uint8_t* enc_out, u
   ge r = rq_load_point(crec);
   if (negated) r = ge_neg(r);
   (void)T;
-  msm_emit_doubled(r, threadIdx.x == 0, enc_out, xyzt_out);
+  if (HALVED) {
+    msm_emit_doubled(r, threadIdx.x == 0, enc_out, xyzt_out);
+    return;
+  }
+  // every lane holds R; the square root's argument on the four rows (row 0 is read back), crec as scratch: two row records,
+  // then row_sqrt_powers' table
+  static_assert(2 + POW_TAB <= 63, "the power table of the square root fits behind two records of crec");
+  uint32_t *xrec = crec, *tab = crec + 2 * RQ_WORDS;
+  const fe den = ge_compress_den(r);
+  __syncthreads();
+  if (t < 4) row::row_store_from_fe(xrec + 16 * t, den);
+  __syncthreads();
+  const row::RowPowers pw = row::row_sqrt_powers(xrec[t], tab, t, K);
+  __syncthreads();
+  xrec[t] = pw.v; xrec[RQ_WORDS + t] = pw.uv;
+  __syncthreads();
+  GivenPowers gp;
+  gp.v = row::row_load_to_fe(xrec); gp.uv = row::row_load_to_fe(xrec + RQ_WORDS);
+  if (t == 0) {
+    if (xyzt_out) store_ge_mont256(xyzt_out, 0, r);
+    uint32_t w8[8];
+    ge_compress(T, gp, r, w8);
+    store32(enc_out, 0, w8);
+  }
 }
 
 // ---- small batches: no buckets -------------------------------------------------------------------------------------
@@ -1629,11 +1739,14 @@ T* msm_at(const MsmCall& c, MsmRegion r) { return reinterpret_cast<T*>(c.d.msm_w
 
 // Phase 1: prepare (points -> affine records, scalars -> digits, written to `dig`) and the counting pass, for the digit type of
 // this window width
+// (sb: bytes per scalar record -- 32, or d377_msm_short's 8 or 16, which take the k_msm_short_prepare_* kernels)
 template <class DT>
-int msm_prepare(const MsmCall& c, bool encoded, const void* pts_in, const uint8_t* scalars, uint8_t* status, DT* dig) {
+int msm_prepare(const MsmCall& c, bool encoded, const void* pts_in, const uint8_t* scalars, uint8_t* status, DT* dig, int sb = 32) {
   DeviceState& d = c.d; const MsmPlan& p = c.p; const hipStream_t s = c.s; const size_t n = c.n;
   const SqrtTables T = d.tables();
   uint32_t* pts = msm_at(c, R_PTS);
+  const bool full = sb == 32;
+  const ScalarsShort sc{scalars, sb};
   if (n) {
     if (encoded) {
       const size_t chunked_min = (size_t)d.tuned(D377_TUNE_MSM_ENC_CHUNKED_MIN, (long long)(d.resident_lanes() * DCB_ASSIST_MIN));
@@ -1651,24 +1764,33 @@ int msm_prepare(const MsmCall& c, bool encoded, const void* pts_in, const uint8_
         GuardScope vb{d.vb_guard, s};                       // the lane-set areas: queue behind their last user
         int r;
         if ((r = vb.acquire())) return r;
-        hipLaunchKernelGGL(k_msm_prepare_enc_chunked<DT>, dim3((unsigned)grid), dim3(BLOCK), 0, s, T, (const uint8_t*)pts_in, scalars, n, p.shape,
-                           pts, dig, status, dcb);
+        if (full) hipLaunchKernelGGL(k_msm_prepare_enc_chunked<DT>, dim3((unsigned)grid), dim3(BLOCK), 0, s, T, (const uint8_t*)pts_in, scalars, n, p.shape,
+                                     pts, dig, status, dcb);
+        else hipLaunchKernelGGL(k_msm_short_prepare_enc_chunked<DT>, dim3((unsigned)grid), dim3(BLOCK), 0, s, T, (const uint8_t*)pts_in, sc, n, p.shape,
+                                pts, dig, status, dcb);
         if ((r = vb.finish())) return r;
-      } else {
+      } else if (full) {
         hipLaunchKernelGGL(k_msm_prepare_enc<DT>, dim3(grid_of(d, n)), dim3(BLOCK), 0, s, T, (const uint8_t*)pts_in, scalars, n, p.shape, pts,
+                           dig, status);
+      } else {
+        hipLaunchKernelGGL(k_msm_short_prepare_enc<DT>, dim3(grid_of(d, n)), dim3(BLOCK), 0, s, T, (const uint8_t*)pts_in, sc, n, p.shape, pts,
                            dig, status);
       }
     } else {
       uint32_t* zflag = msm_at(c, R_FLAG);
       HIP_TRY(hipMemsetAsync(zflag, 0, sizeof(uint32_t), s));
-      hipLaunchKernelGGL(k_msm_prepare_affine<DT>, dim3(grid_of(d, n)), dim3(BLOCK), 0, s, T, (const uint64_t*)pts_in, scalars, n, p.shape, pts,
-                         dig, zflag);
+      if (full) hipLaunchKernelGGL(k_msm_prepare_affine<DT>, dim3(grid_of(d, n)), dim3(BLOCK), 0, s, T, (const uint64_t*)pts_in, scalars, n, p.shape, pts,
+                                   dig, zflag);
+      else hipLaunchKernelGGL(k_msm_short_prepare_affine<DT>, dim3(grid_of(d, n)), dim3(BLOCK), 0, s, T, (const uint64_t*)pts_in, sc, n, p.shape, pts,
+                              dig, zflag);
       // ~32 elements per lane share one inversion, but never fewer lanes than one wave per SIMD (see k_to_affine)
       size_t lanes = (n + 31) / 32;
       const size_t fill = (size_t)d.cus * BLOCK;
       if (lanes < fill) lanes = fill < n ? fill : n;
-      hipLaunchKernelGGL(k_msm_prepare_el<DT>, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, (const uint64_t*)pts_in,
-                         scalars, n, p.shape, pts, dig, zflag);
+      if (full) hipLaunchKernelGGL(k_msm_prepare_el<DT>, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, (const uint64_t*)pts_in,
+                                   scalars, n, p.shape, pts, dig, zflag);
+      else hipLaunchKernelGGL(k_msm_short_prepare_el<DT>, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, (const uint64_t*)pts_in,
+                              sc, n, p.shape, pts, dig, zflag);
     }
   }
   return D377_OK;
@@ -1683,9 +1805,9 @@ int msm_count(const MsmCall& c) {
   return D377_OK;
 }
 template <class DT>
-int msm_prepare_count(const MsmCall& c, bool encoded, const void* pts_in, const uint8_t* scalars, uint8_t* status) {
+int msm_prepare_count(const MsmCall& c, bool encoded, const void* pts_in, const uint8_t* scalars, uint8_t* status, int sb) {
   int rc;
-  if ((rc = msm_prepare<DT>(c, encoded, pts_in, scalars, status, msm_at<DT>(c, R_DIGITS)))) return rc;
+  if ((rc = msm_prepare<DT>(c, encoded, pts_in, scalars, status, msm_at<DT>(c, R_DIGITS), sb))) return rc;
   return msm_count<DT>(c);
 }
 
@@ -1752,7 +1874,7 @@ int msm_bucket_records(const MsmCall& c) {
     hipLaunchKernelGGL(k_msm_buckets<2>, dim3(grid_of(d, (size_t)W * nb * 2)), dim3(BLOCK), 0, s, lv, sp, segoff, lvlmax, p.red.skip, W, nb, bkt, meta);
   return D377_OK;
 }
-int msm_sums(const MsmCall& c, uint8_t* enc_out, uint64_t* xyzt_out) {
+int msm_sums(const MsmCall& c, uint8_t* enc_out, uint64_t* xyzt_out, bool halved = true) {
   DeviceState& d = c.d; const MsmPlan& p = c.p; const hipStream_t s = c.s;
   const int W = p.W, nb = p.nb;
   int rc;
@@ -1787,7 +1909,8 @@ int msm_sums(const MsmCall& c, uint8_t* enc_out, uint64_t* xyzt_out) {
       cur_in = o;
     }
   }
-  hipLaunchKernelGGL(k_msm_final, dim3(1), dim3(64), 0, s, d.tables(), cur_in, p.shape, enc_out, xyzt_out);
+  if (halved) hipLaunchKernelGGL(k_msm_final<true>, dim3(1), dim3(64), 0, s, d.tables(), cur_in, p.shape, enc_out, xyzt_out);
+  else hipLaunchKernelGGL(k_msm_final<false>, dim3(1), dim3(64), 0, s, d.tables(), cur_in, p.shape, enc_out, xyzt_out);
   return D377_OK;
 }
 
@@ -1802,34 +1925,55 @@ int msm_span_blocks(DeviceState& d) {
   return D377_OK;
 }
 
-// everything on device pointers, enqueued on `s`
-int msm_launch(DeviceState& d, hipStream_t s, bool encoded, const void* pts_in, const uint8_t* scalars, size_t n,
-               uint8_t* enc_out, uint64_t* xyzt_out, uint8_t* status) {
-  if (n >= ((size_t)1 << 31)) return fail(D377_ERR_ARG, "%s", "msm: n must be below 2^31");
-  if (n && n <= msm_small_max(d, encoded) && n < ((size_t)1 << 24)) return msm_launch_small(d, s, encoded, pts_in, scalars, n, enc_out, xyzt_out, status);
+// The window width the short forms ask the plan for: pick_window's rule by n (the cost per window does not depend on how many
+// there are), never beyond 16 bits -- the plan then takes the narrowest width that tiles the bits with as many windows
+// (msm_plan.hpp: win_shape_bits), so the digits are int16 whatever the override says.
+int pick_window_short(const DeviceState& d, size_t n) {
+  const int c = pick_window(d, n);
+  return c > 16 ? 16 : c;
+}
+
+// what msm_launch's plan is made from: n, the width, the scalar bits, the device and the developer overrides
+int msm_plan_in(DeviceState& d, size_t n, int sb, MsmPlanIn* out) {
   MsmPlanIn in;
-  in.n = n; in.c = pick_window(d, n); in.cus = d.cus;
+  in.n = n; in.cus = d.cus;
+  if (sb == 32) in.c = pick_window(d, n);
+  else { in.c = pick_window_short(d, n); in.bits = short_scalar_bits(sb); }
   int rc;
   if ((rc = msm_span_blocks(d))) return rc;
   in.span_blocks = d.msm_span_blocks;
   in.slices = d.tuned(D377_TUNE_MSM_SLICES, PLAN_DEFAULT); in.seg = d.tuned(D377_TUNE_MSM_SEG, PLAN_DEFAULT);   // developer overrides (sweeps)
   in.red = d.tuned(D377_TUNE_MSM_RED, PLAN_DEFAULT); in.skip = d.tuned(D377_TUNE_MSM_SKIP, PLAN_DEFAULT);
   in.chunked_sums = d.tuned(D377_TUNE_MSM_CHUNKED_SUMS, PLAN_DEFAULT); in.sort_packed = d.tuned(D377_TUNE_MSM_SORT_PACKED, PLAN_DEFAULT);
+  *out = in;
+  return D377_OK;
+}
+
+// everything on device pointers, enqueued on `s`.  sb: bytes per scalar record, 32 (d377_msm) or 8 / 16 (d377_msm_short: the
+// buckets at every n -- the wave routes form k / 2 mod r and are the 32-byte form's)
+int msm_launch(DeviceState& d, hipStream_t s, bool encoded, const void* pts_in, const uint8_t* scalars, size_t n,
+               uint8_t* enc_out, uint64_t* xyzt_out, uint8_t* status, int sb = 32) {
+  if (n >= ((size_t)1 << 31)) return fail(D377_ERR_ARG, "%s", "msm: n must be below 2^31");
+  if (sb == 32 && n && n <= msm_small_max(d, encoded) && n < ((size_t)1 << 24))
+    return msm_launch_small(d, s, encoded, pts_in, scalars, n, enc_out, xyzt_out, status);
+  MsmPlanIn in;
+  int rc;
+  if ((rc = msm_plan_in(d, n, sb, &in))) return rc;
   const MsmPlan p = msm_plan(in);
   GuardScope held{d.msm_guard, s};
   if ((rc = msm_reserve(d, s, p.bytes)) || (rc = held.acquire())) return rc;
   const MsmCall call{d, s, p, n};
-  if ((rc = p.wide_digits ? msm_prepare_count<int32_t>(call, encoded, pts_in, scalars, status)
-                          : msm_prepare_count<int16_t>(call, encoded, pts_in, scalars, status))) return rc;
+  if ((rc = p.wide_digits ? msm_prepare_count<int32_t>(call, encoded, pts_in, scalars, status, sb)
+                          : msm_prepare_count<int16_t>(call, encoded, pts_in, scalars, status, sb))) return rc;
   if ((rc = msm_scan_place(call))) return rc;
-  if ((rc = msm_sums(call, enc_out, xyzt_out))) return rc;
+  if ((rc = msm_sums(call, enc_out, xyzt_out, sb == 32))) return rc;
   HIP_TRY(hipGetLastError());
   return held.finish();
 }
 
 // one device's share of a host batch: copies in, MSM, partial sum (Element record) and statuses out, synchronised
 int msm_one(DeviceState& d, bool encoded, const uint8_t* pts_in, const uint8_t* scalars, size_t cnt, uint8_t* enc_out,
-            uint64_t* partial_out, uint8_t* status) {
+            uint64_t* partial_out, uint8_t* status, int sb) {
   HIP_TRY(hipSetDevice(d.id));
   int rc = D377_OK;
   SyncOnError guard{&rc, d.id, d.stream, nullptr};
@@ -1837,16 +1981,16 @@ int msm_one(DeviceState& d, bool encoded, const uint8_t* pts_in, const uint8_t* 
     const size_t rec = encoded ? 32 : 128;
     int r;
     if ((r = ensure(d, 0, cnt * rec + 16))) return r;
-    if ((r = ensure(d, 1, cnt * 32 + 16))) return r;
+    if ((r = ensure(d, 1, cnt * (size_t)sb + 16))) return r;
     if ((r = ensure(d, 2, 32 + 128))) return r;
     if ((r = ensure(d, 3, cnt + 16))) return r;
     StarveCheck starve{d, d.stream};
     if ((r = starve.before())) return r;
     if (cnt) {
       HIP_TRY(hipMemcpyAsync(d.buf[0], pts_in, cnt * rec, hipMemcpyHostToDevice, d.stream));
-      HIP_TRY(hipMemcpyAsync(d.buf[1], scalars, cnt * 32, hipMemcpyHostToDevice, d.stream));
+      HIP_TRY(hipMemcpyAsync(d.buf[1], scalars, cnt * (size_t)sb, hipMemcpyHostToDevice, d.stream));
     }
-    if ((r = msm_launch(d, d.stream, encoded, d.buf[0], d.buf[1], cnt, d.buf[2], (uint64_t*)(d.buf[2] + 32), d.buf[3]))) return r;
+    if ((r = msm_launch(d, d.stream, encoded, d.buf[0], d.buf[1], cnt, d.buf[2], (uint64_t*)(d.buf[2] + 32), d.buf[3], sb))) return r;
     HIP_TRY(hipMemcpyAsync(partial_out, d.buf[2] + 32, 128, hipMemcpyDeviceToHost, d.stream));
     if (encoded && cnt) HIP_TRY(hipMemcpyAsync(status, d.buf[3], cnt, hipMemcpyDeviceToHost, d.stream));
     if (enc_out) HIP_TRY(hipMemcpyAsync(enc_out, d.buf[2], 32, hipMemcpyDeviceToHost, d.stream));
@@ -1859,7 +2003,7 @@ int msm_one(DeviceState& d, bool encoded, const uint8_t* pts_in, const uint8_t* 
 }
 
 int msm_host(d377_ctx* ctx, bool encoded, const void* pts_in, const uint8_t* scalars, size_t n, uint8_t* enc_out,
-             uint64_t* xyzt_out, uint8_t* status) {
+             uint64_t* xyzt_out, uint8_t* status, int sb = 32) {
   if (!ctx) return fail(D377_ERR_ARG, "%s", "null context");
   if (!enc_out || (n && (!pts_in || !scalars)) || (encoded && n && !status)) return fail(D377_ERR_ARG, "%s", "null buffer");
   std::lock_guard<std::mutex> lock(ctx->mu);
@@ -1868,7 +2012,7 @@ int msm_host(d377_ctx* ctx, bool encoded, const void* pts_in, const uint8_t* sca
   std::vector<uint64_t> partial(nd * 16, 0);
   int rc;
   if (nd == 1) {
-    if ((rc = msm_one(ctx->devs[0], encoded, (const uint8_t*)pts_in, scalars, n, enc_out, partial.data(), status))) return rc;
+    if ((rc = msm_one(ctx->devs[0], encoded, (const uint8_t*)pts_in, scalars, n, enc_out, partial.data(), status, sb))) return rc;
     if (xyzt_out) memcpy(xyzt_out, partial.data(), 128);
     return D377_OK;
   }
@@ -1887,8 +2031,8 @@ int msm_host(d377_ctx* ctx, bool encoded, const void* pts_in, const uint8_t* sca
     ++used;
     workers.emplace_back([&, k, lo, cnt]() {
       if (delay > 0) std::this_thread::sleep_for(std::chrono::milliseconds(delay));
-      rcs[k] = msm_one(ctx->devs[k], encoded, (const uint8_t*)pts_in + lo * rec, scalars + lo * 32, cnt, nullptr,
-                       partial.data() + 16 * k, (encoded && cnt) ? status + lo : nullptr);
+      rcs[k] = msm_one(ctx->devs[k], encoded, (const uint8_t*)pts_in + lo * rec, scalars + lo * (size_t)sb, cnt, nullptr,
+                       partial.data() + 16 * k, (encoded && cnt) ? status + lo : nullptr, sb);
       if (rcs[k] != D377_OK) errs[k] = d377_g_err;
     });
   }
@@ -1918,16 +2062,42 @@ int msm_host(d377_ctx* ctx, bool encoded, const void* pts_in, const uint8_t* sca
 }
 
 int msm_dev(d377_ctx* ctx, int dev, void* stream, bool encoded, const void* pts_in, const uint8_t* scalars, size_t n,
-            uint8_t* enc_out, uint64_t* xyzt_out, uint8_t* status) {
+            uint8_t* enc_out, uint64_t* xyzt_out, uint8_t* status, int sb = 32) {
   if (!ctx) return fail(D377_ERR_ARG, "%s", "null context");
   if (dev < 0 || (size_t)dev >= ctx->devs.size()) return fail(D377_ERR_ARG, "%s", "device index out of range");
   if (!enc_out || (n && (!pts_in || !scalars)) || (encoded && n && !status)) return fail(D377_ERR_ARG, "%s", "null buffer");
-  if (!aligned16(pts_in) || !aligned16(scalars) || !aligned16(enc_out) || !aligned16(xyzt_out))
+  if (sb != 32 && (reinterpret_cast<uintptr_t>(scalars) & (uintptr_t)(sb - 1)) != 0)
+    return fail(D377_ERR_ARG, "%s", sb == 8 ? "msm_short: scalars must be aligned to scalar_bytes (8) on the device"
+                                            : "msm_short: scalars must be aligned to scalar_bytes (16) on the device");
+  if (!aligned16(pts_in) || (sb == 32 && !aligned16(scalars)) || !aligned16(enc_out) || !aligned16(xyzt_out))
     return fail(D377_ERR_ARG, "%s", "device record buffers must be 16-byte aligned");
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceState& d = ctx->devs[(size_t)dev];
   HIP_TRY(hipSetDevice(d.id));
-  return msm_launch(d, (hipStream_t)stream, encoded, pts_in, scalars, n, enc_out, xyzt_out, status);
+  return msm_launch(d, (hipStream_t)stream, encoded, pts_in, scalars, n, enc_out, xyzt_out, status, sb);
+}
+
+// d377_msm_short's own checks, in the order the header gives: the scalar length, then null buffers and n -- both before any
+// device is touched -- and only then the context (msm_host / msm_dev)
+int msm_short_bad_bytes(const char* who, int scalar_bytes) {
+  char msg[160];
+  snprintf(msg, sizeof msg, "%s: scalar_bytes must be 8 or 16 (got %d)", who, scalar_bytes);
+  return fail(D377_ERR_ARG, "%s", msg);
+}
+int msm_short_null(const char* who, const char* what) {
+  char msg[160];
+  snprintf(msg, sizeof msg, "%s: null buffer: %s", who, what);
+  return fail(D377_ERR_ARG, "%s", msg);
+}
+int msm_short_args(const char* who, int scalar_bytes, const void* pts_in, const uint8_t* scalars, size_t n, const uint8_t* enc_out,
+                   bool encoded, const uint8_t* status) {
+  if (scalar_bytes != 8 && scalar_bytes != 16) return msm_short_bad_bytes(who, scalar_bytes);
+  if (!enc_out) return msm_short_null(who, "enc32_out");
+  if (n && !pts_in) return msm_short_null(who, encoded ? "enc32" : "xyzt");
+  if (n && !scalars) return msm_short_null(who, "scalars");
+  if (encoded && n && !status) return msm_short_null(who, "status");
+  if (n >= ((size_t)1 << 31)) return fail(D377_ERR_ARG, "%s: n must be below 2^31", who);
+  return D377_OK;
 }
 
 }  // namespace
@@ -1949,6 +2119,47 @@ int d377_msm_dev(d377_ctx* ctx, int dev, void* stream, const uint64_t* xyzt, con
 int d377_msm_encoded_dev(d377_ctx* ctx, int dev, void* stream, const uint8_t* enc32, const uint8_t* scalar32, size_t n,
                          uint8_t* enc32_out, uint64_t* xyzt_out, uint8_t* status) {
   return msm_dev(ctx, dev, stream, true, enc32, scalar32, n, enc32_out, xyzt_out, status);
+}
+int d377_msm_short(d377_ctx* ctx, const uint64_t* xyzt, const uint8_t* scalars, int scalar_bytes, size_t n, uint8_t* enc32_out,
+                   uint64_t* xyzt_out) {
+  int rc;
+  if ((rc = msm_short_args("d377_msm_short", scalar_bytes, xyzt, scalars, n, enc32_out, false, nullptr))) return rc;
+  return msm_host(ctx, false, xyzt, scalars, n, enc32_out, xyzt_out, nullptr, scalar_bytes);
+}
+int d377_msm_short_encoded(d377_ctx* ctx, const uint8_t* enc32, const uint8_t* scalars, int scalar_bytes, size_t n, uint8_t* enc32_out,
+                           uint64_t* xyzt_out, uint8_t* status) {
+  int rc;
+  if ((rc = msm_short_args("d377_msm_short_encoded", scalar_bytes, enc32, scalars, n, enc32_out, true, status))) return rc;
+  return msm_host(ctx, true, enc32, scalars, n, enc32_out, xyzt_out, status, scalar_bytes);
+}
+int d377_msm_short_dev(d377_ctx* ctx, int dev, void* stream, const uint64_t* xyzt, const uint8_t* scalars, int scalar_bytes, size_t n,
+                       uint8_t* enc32_out, uint64_t* xyzt_out) {
+  int rc;
+  if ((rc = msm_short_args("d377_msm_short_dev", scalar_bytes, xyzt, scalars, n, enc32_out, false, nullptr))) return rc;
+  return msm_dev(ctx, dev, stream, false, xyzt, scalars, n, enc32_out, xyzt_out, nullptr, scalar_bytes);
+}
+int d377_msm_short_encoded_dev(d377_ctx* ctx, int dev, void* stream, const uint8_t* enc32, const uint8_t* scalars, int scalar_bytes, size_t n,
+                               uint8_t* enc32_out, uint64_t* xyzt_out, uint8_t* status) {
+  int rc;
+  if ((rc = msm_short_args("d377_msm_short_encoded_dev", scalar_bytes, enc32, scalars, n, enc32_out, true, status))) return rc;
+  return msm_dev(ctx, dev, stream, true, enc32, scalars, n, enc32_out, xyzt_out, status, scalar_bytes);
+}
+int d377_msm_short_plan(d377_ctx* ctx, int dev, size_t n, int scalar_bytes, int* window_bits_used, int* windows, uint64_t* workspace_bytes) {
+  if (scalar_bytes != 8 && scalar_bytes != 16) return msm_short_bad_bytes("d377_msm_short_plan", scalar_bytes);
+  if (n >= ((size_t)1 << 31)) return fail(D377_ERR_ARG, "%s", "d377_msm_short_plan: n must be below 2^31");
+  if (!ctx) return fail(D377_ERR_ARG, "%s", "null context");
+  if (dev < 0 || (size_t)dev >= ctx->devs.size()) return fail(D377_ERR_ARG, "%s", "device index out of range");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceState& d = ctx->devs[(size_t)dev];
+  HIP_TRY(hipSetDevice(d.id));
+  MsmPlanIn in;
+  int rc;
+  if ((rc = msm_plan_in(d, n, scalar_bytes, &in))) return rc;
+  const MsmPlan p = msm_plan(in);
+  if (window_bits_used) *window_bits_used = p.shape.c;
+  if (windows) *windows = p.W;
+  if (workspace_bytes) *workspace_bytes = (uint64_t)p.bytes;
+  return D377_OK;
 }
 int d377_sum_elements_dev(d377_ctx* ctx, int dev, void* stream, const uint64_t* xyzt, size_t m, uint8_t* enc32_out,
                           uint64_t* xyzt_out) {

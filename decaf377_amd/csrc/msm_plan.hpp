@@ -22,10 +22,20 @@ struct WinShape {
   D377_HD int width(int w) const { return w < nwide ? c : c - 1; }
   D377_HD int first_bit(int w) const { return w * c - (w > nwide ? w - nwide : 0); }
 };
-inline WinShape win_shape(int c) {
-  const int W = (252 + c - 1) / c;
-  return WinShape{c, W, W - (W * c - 252)};
+// The same cut for any bit count B (d377_msm_short: B = 8 * scalar_bytes + 1, the extra bit being the room the unwrapped top
+// window needs for the carry of the signed digits below it): W = ceil(B / c) windows of the NARROWEST width c' = ceil(B / W)
+// with which W windows tile B, the first nwide of them c' bits and the rest c' - 1 (65 bits at c = 16: five 13-bit windows,
+// where "c and c - 1" would have to drop 15 bits from 5 windows).  The shape carries c': buckets per window, the digit type
+// and the tree's depth follow it.  For B = 252 and every c in 4 .. 18, c' = c: win_shape(c) below is what it always was
+// (tests/test_msm_short_host.py pins that).
+constexpr int FR_BITS = 252;
+inline WinShape win_shape_bits(int B, int c) {
+  const int W = (B + c - 1) / c;
+  const int cn = (B + W - 1) / W;
+  return WinShape{cn, W, W - (W * cn - B)};
 }
+inline WinShape win_shape(int c) { return win_shape_bits(FR_BITS, c); }
+inline int short_scalar_bits(int scalar_bytes) { return 8 * scalar_bytes + 1; }
 // signed digit w of k (< 2^252): |digit| <= 2^(width - 1); the top window is not wrapped
 D377_HD int msm_digit(const uint32_t k[8], int w, const WinShape& ws, uint32_t& carry) {
   const int bit = ws.first_bit(w), cw = ws.width(w);
@@ -126,6 +136,8 @@ struct MsmPlanIn {
   // SUMS that share the pipeline (msm_batch_plan.hpp): n points, n / sums per sum, under composite bucket keys -- sum k owns the
   // buckets k 2^(c-1) + 1 .. (k + 1) 2^(c-1) of every window.  One sum (the default) is d377_msm's plan, unchanged.
   size_t sums = 1;
+  // scalar bits the windows tile: 252 (k / 2 mod r of any scalar), or short_scalar_bits() for d377_msm_short's 8- and 16-byte scalars
+  int bits = FR_BITS;
 };
 struct MsmPlan {
   WinShape shape; int W, nb;             // the windows; bucket indices 0 .. sums * 2^(c-1)
@@ -151,8 +163,9 @@ struct MsmPlan {
 inline MsmPlan msm_plan(const MsmPlanIn& in) {
   auto tuned = [](long long v, long long dflt) { return v >= 0 ? v : dflt; };
   MsmPlan p{};
-  const size_t n = in.n; const int c = in.c;
-  p.shape = win_shape(c);                                      // W windows of c or c - 1 bits that tile the 252 scalar bits
+  const size_t n = in.n;
+  p.shape = win_shape_bits(in.bits, in.c);                     // W windows of c or c - 1 bits that tile the scalar bits
+  const int c = p.shape.c;                                     // (in.c for the 252 bits of a full scalar; no wider for short ones)
   const int W = p.W = p.shape.W;
   const size_t K = p.sums = in.sums < 1 ? 1 : in.sums;         // (msm_batch_plan.hpp keeps K 2^(c-1) within the sort's 2^17)
   const int nb = p.nb = (int)(K << (c - 1)) + 1;

@@ -912,6 +912,81 @@ class Context:
         _native.check(self._lib.d377_msm(self._h, p(pts), p(sc), ctypes.c_size_t(n), p(enc), p(xyzt)))
         return enc, xyzt, None
 
+    @staticmethod
+    def _short_scalars(scalars, n, device):
+        """The scalars of msm_short as n packed little-endian records -> (contiguous array or tensor, bytes per record).
+        [n, 8] or [n, 16] uint8, or uint64 of shape [n] / [n, 2] (little-endian words; int64 tensors count as uint64)."""
+        torch_in = _is_torch(scalars)
+        if device is not None and (not torch_in or scalars.device != device):
+            raise ValueError("msm_short scalars: expected a tensor on %s" % (device,))
+        if device is None and torch_in:
+            raise ValueError("msm_short scalars: a tensor goes with points on a device of the context")
+        shape = tuple(int(x) for x in scalars.shape)
+        if torch_in:
+            import torch
+            is_u8, is_u64 = scalars.dtype == torch.uint8, scalars.dtype in (torch.int64, torch.uint64)
+        else:
+            is_u8, is_u64 = scalars.dtype == np.uint8, scalars.dtype in (np.uint64, np.int64)
+        if is_u8 and shape in ((n, 8), (n, 16)):
+            nbytes = shape[1]
+        elif is_u64 and shape in ((n,), (n, 1), (n, 2)):
+            nbytes = 16 if shape == (n, 2) else 8
+        else:
+            raise ValueError("msm_short scalars: expected [%d, 8] or [%d, 16] uint8, or uint64 of shape [%d] or [%d, 2], got %s %s"
+                             % (n, n, n, n, scalars.dtype, shape))
+        return (scalars.contiguous() if torch_in else np.ascontiguousarray(scalars)), nbytes
+
+    def msm_short(self, points, scalars, encoded=None):
+        """msm() over scalars known to be short (d377_msm_short[_encoded], include/decaf377_amd_short_msm.h): the weights of a
+        batch verification (128 bits), amounts (u64 / u128).  The bytes returned are those of msm() on the same scalars
+        zero-extended to 32 bytes, from 5 or 9 windows of digits instead of 16.
+        points: [n, 16] u64 Elements or [n, 32] u8 Encodings (detected by the row width).
+        scalars: [n, 8] or [n, 16] uint8, or uint64 of shape [n] / [n, 2] (little-endian words).
+        Tensors on a device of the context take the _dev form on torch's current stream (one eager call of a shape before
+        capturing it in a graph).  Returns (enc[32] u8, xyzt[16] u64, status[n] or None)."""
+        n = _rows(points)
+        if points.ndim != 2 or int(points.shape[1]) not in (16, 32):
+            raise ValueError("msm_short: points must be [n, 16] Elements or [n, 32] Encodings")
+        if encoded is None:
+            encoded = int(points.shape[1]) == 32
+        _check(points, ENC if encoded else ELEM, n, "msm_short points")
+        sz, nb = ctypes.c_size_t(n), None
+        if _is_torch(points):
+            import torch
+            dev = points.device
+            di = self._dev_index(dev)
+            sc, nb = self._short_scalars(scalars, n, dev)
+            pts = points.contiguous()
+            enc = torch.empty((32,), dtype=torch.uint8, device=dev)
+            xyzt = torch.empty((16,), dtype=torch.int64, device=dev)
+            st = torch.empty((max(n, 1),), dtype=torch.uint8, device=dev) if encoded else None
+            stream = _torch_stream(dev)
+            p = lambda t: ctypes.c_void_p(t.data_ptr())
+            if encoded:
+                _native.check(self._lib.d377_msm_short_encoded_dev(self._h, di, stream, p(pts), p(sc), nb, sz, p(enc), p(xyzt), p(st)))
+                return enc, xyzt, st[:n]
+            _native.check(self._lib.d377_msm_short_dev(self._h, di, stream, p(pts), p(sc), nb, sz, p(enc), p(xyzt)))
+            return enc, xyzt, None
+        sc, nb = self._short_scalars(scalars, n, None)
+        pts = np.ascontiguousarray(points)
+        enc = np.zeros(32, np.uint8)
+        xyzt = np.zeros(16, np.uint64)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        if encoded:
+            st = np.zeros(max(n, 1), np.uint8)
+            _native.check(self._lib.d377_msm_short_encoded(self._h, p(pts), p(sc), nb, sz, p(enc), p(xyzt), p(st)))
+            return enc, xyzt, st[:n]
+        _native.check(self._lib.d377_msm_short(self._h, p(pts), p(sc), nb, sz, p(enc), p(xyzt)))
+        return enc, xyzt, None
+
+    def msm_short_plan(self, n, scalar_bytes, dev=0):
+        """The plan of msm_short for n terms of 8- or 16-byte scalars on device `dev` of the context (d377_msm_short_plan) ->
+        {"window_bits", "windows", "workspace_bytes"}."""
+        c, w, ws = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_uint64(0)
+        _native.check(self._lib.d377_msm_short_plan(self._h, int(dev), ctypes.c_size_t(int(n)), int(scalar_bytes), ctypes.byref(c),
+                                                    ctypes.byref(w), ctypes.byref(ws)))
+        return {"window_bits": c.value, "windows": w.value, "workspace_bytes": ws.value}
+
     def sum_elements(self, xyzt):
         """Sum of m Element records held in HBM -> (enc[32], xyzt[16]); used to combine the
         per-rank partial sums of a sharded MSM."""

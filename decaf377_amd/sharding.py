@@ -117,7 +117,8 @@ def msm_sharded(ctx, points, scalars, group=None):
     """vartime_multiscalar_mul over points sharded across ranks: local Pippenger MSM on this
     rank's shard, all-gather of the per-rank partial sums (RCCL over xGMI for HBM tensors),
     then every rank adds the `world` partial points and compresses.  Returns enc[32] (same on
-    every rank)."""
+    every rank).  Scalars are 32-byte records: the short-scalar sum (Context.msm_short) has no rank-parallel form; a rank
+    that holds short scalars can call it on its shard and pass the partial Element records to allgather_partials itself."""
     _, partial, _ = ctx.msm(points, scalars)
     if not dist.is_initialized() or dist.get_world_size(group) == 1:
         enc, _ = ctx.sum_elements(partial.reshape(1, 16))

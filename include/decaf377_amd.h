@@ -618,5 +618,6 @@ int d377_batch_sharded_dev(d377_ctx* ctx, int root_dev, void* stream, int op, co
 #include "decaf377_amd_bucket_sums.h"
 #include "decaf377_amd_ragged_sums.h"
 #include "decaf377_amd_segmented_sums.h"
+#include "decaf377_amd_short_msm.h"
 
 #endif /* DECAF377_AMD_H */

@@ -483,6 +483,34 @@ class Engine {
     st.resize(points.size());
     return {out, results(points, st)};
   }
+  /// The same over scalars that are SHORT by their type -- uint64_t or unsigned __int128: the weights of a batch verification,
+  /// amounts (d377_msm_short, decaf377_amd_short_msm.h).  The Element (and Encoding) is that of vartime_multiscalar_mul on the
+  /// same values, from 5 or 9 windows of digits instead of 16.  Scalars are passed as they lie in memory (little-endian hosts).
+  Element vartime_multiscalar_mul_short(const std::vector<uint64_t>& scalars, const std::vector<Element>& points, Encoding* encoding = nullptr) {
+    return msm_short_host(scalars.data(), 8, scalars.size(), points, encoding);
+  }
+  Element vartime_multiscalar_mul_short(const std::vector<unsigned __int128>& scalars, const std::vector<Element>& points,
+                                        Encoding* encoding = nullptr) {
+    return msm_short_host(scalars.data(), 16, scalars.size(), points, encoding);
+  }
+  /// ... 16-byte little-endian records, for callers that hold their u128 values as bytes
+  Element vartime_multiscalar_mul_short(const std::vector<std::array<uint8_t, 16>>& scalars, const std::vector<Element>& points,
+                                        Encoding* encoding = nullptr) {
+    return msm_short_host(scalars.data(), 16, scalars.size(), points, encoding);
+  }
+  /// ... on DEVICE pointers of device `dev` of the Engine: `scalars` holds n records of scalar_bytes (8 or 16) bytes and is
+  /// aligned to that, the other records 16-byte aligned; enqueues on `stream` and returns.  d377_msm_dev's workspace rules: one
+  /// eager call of a shape before it is captured into a graph.
+  void msm_short_resident(int dev, void* stream, const Element* points, const void* scalars, int scalar_bytes, size_t n, Encoding* enc_out,
+                          Element* element_out = nullptr) {
+    check(d377_msm_short_dev(ctx_, dev, stream, reinterpret_cast<const uint64_t*>(points), static_cast<const uint8_t*>(scalars), scalar_bytes, n,
+                             reinterpret_cast<uint8_t*>(enc_out), reinterpret_cast<uint64_t*>(element_out)));
+  }
+  void msm_short_resident(int dev, void* stream, const Encoding* points, const void* scalars, int scalar_bytes, size_t n, Encoding* enc_out,
+                          Element* element_out, uint8_t* status) {
+    check(d377_msm_short_encoded_dev(ctx_, dev, stream, reinterpret_cast<const uint8_t*>(points), static_cast<const uint8_t*>(scalars), scalar_bytes,
+                                     n, reinterpret_cast<uint8_t*>(enc_out), reinterpret_cast<uint64_t*>(element_out), status));
+  }
   /// MANY small sums at once: sum i = scalars[i m ..][..m] . points[i m ..][..m], m terms each (1 .. 8) -- the shape of the
   /// crate's own multiscalar test, a 3-term sum per case (tests/operations.rs:44-60).  The sums come back as Elements, as
   /// the crate's function returns them; `encodings`, if given, receives their Encodings, which the same pass computes.
@@ -664,6 +692,14 @@ class Engine {
   template <class T> static uint8_t* u8m(std::vector<T>& v) { return reinterpret_cast<uint8_t*>(v.data()); }
   static const uint64_t* u64(const std::vector<Element>& v) { return reinterpret_cast<const uint64_t*>(v.data()); }
   static void check(int rc) { if (rc != D377_OK) throw DeviceError(rc); }
+  Element msm_short_host(const void* scalars, int scalar_bytes, size_t n, const std::vector<Element>& points, Encoding* encoding) {
+    if (n != points.size()) throw std::invalid_argument("length mismatch");
+    Element out;
+    Encoding enc;
+    check(d377_msm_short(ctx_, u64(points), static_cast<const uint8_t*>(scalars), scalar_bytes, n, enc.b.data(), out.xyzt.data()));
+    if (encoding) *encoding = enc;
+    return out;
+  }
   template <class T>
   static std::vector<Result<T>> results(const std::vector<T>& v, const std::vector<uint8_t>& st) {
     std::vector<Result<T>> r(v.size());

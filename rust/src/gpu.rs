@@ -44,6 +44,22 @@ pub mod ffi_bucket_sums;                                          // rust/src/ff
 pub mod ffi_ragged_sums;                                          // rust/src/ffi_ragged_sums.rs, from include/decaf377_amd_ragged_sums.h
 #[path = "gpu/ffi_segmented_sums.rs"]
 pub mod ffi_segmented_sums;                                       // rust/src/ffi_segmented_sums.rs, from include/decaf377_amd_segmented_sums.h
+#[path = "gpu/ffi_short_msm.rs"]
+pub mod ffi_short_msm;                                            // rust/src/ffi_short_msm.rs, from include/decaf377_amd_short_msm.h
+
+/// A scalar that is short by its type -- `u64` or `u128` -- as d377_msm_short reads it: BYTES little-endian bytes, no reduction.
+pub trait ShortScalar: Copy {
+    const BYTES: i32;
+    fn write_le(self, out: &mut Vec<u8>);
+}
+impl ShortScalar for u64 {
+    const BYTES: i32 = 8;
+    fn write_le(self, out: &mut Vec<u8>) { out.extend_from_slice(&self.to_le_bytes()); }
+}
+impl ShortScalar for u128 {
+    const BYTES: i32 = 16;
+    fn write_le(self, out: &mut Vec<u8>) { out.extend_from_slice(&self.to_le_bytes()); }
+}
 
 /// Which backend's root `sqrt_ratio_zeta_batch` returns (the flags are the same).
 #[derive(Copy, Clone, Debug, PartialEq, Eq)]
@@ -476,6 +492,20 @@ impl Element {
         check(unsafe { ffi::d377_msm(ctx.0, xyzt.as_ptr(), bytes.as_ptr(), points.len(), enc.as_mut_ptr(), out.as_mut_ptr()) })?;
         Ok(element_from_xyzt(&out))
     }
+    /// `vartime_multiscalar_mul` over scalars that are short by their type (`&[u64]` or `&[u128]`: the weights of a batch
+    /// verification, amounts): d377_msm_short, the same Element from 5 or 9 windows of digits instead of 16.
+    pub fn vartime_multiscalar_mul_short_gpu<S: ShortScalar>(ctx: &GpuContext, scalars: &[S], points: &[Element]) -> Result<Element, GpuError> {
+        assert_eq!(scalars.len(), points.len());
+        let xyzt = elements_to_xyzt(points);
+        let mut bytes = Vec::with_capacity(scalars.len() * S::BYTES as usize);
+        for k in scalars { k.write_le(&mut bytes); }
+        let mut enc = [0u8; 32];
+        let mut out = [0u64; 16];
+        check(unsafe {
+            ffi_short_msm::d377_msm_short(ctx.0, xyzt.as_ptr(), bytes.as_ptr(), S::BYTES, points.len(), enc.as_mut_ptr(), out.as_mut_ptr())
+        })?;
+        Ok(element_from_xyzt(&out))
+    }
     /// The same over Encodings: invalid ones are reported and left out of the sum.
     pub fn vartime_multiscalar_mul_encoded_gpu(ctx: &GpuContext, scalars: &[Fr], points: &[Encoding])
         -> Result<(Element, Vec<Result<(), EncodingError>>), GpuError> {
@@ -891,5 +921,17 @@ pub mod dev {
         assert!(!offsets.is_empty());
         check(ffi_segmented_sums::d377_batch_segmented_msm_encoded_resident(ctx.0, dev, stream, enc32, scalar32, offsets.as_ptr(),
                                                                             offsets_dev, offsets.len() - 1, enc32_out, xyzt_out, status))
+    }
+
+    // The one long sum over 8- or 16-byte scalars on device buffers (ffi_short_msm.rs): msm's contract and workspace rules;
+    // `scalars` holds n records of `scalar_bytes` bytes and is aligned to that; `xyzt_out` may be null.
+    pub unsafe fn msm_short_resident(ctx: &GpuContext, dev: i32, stream: *mut c_void, xyzt: *const u64, scalars: *const u8, scalar_bytes: i32,
+                                     n: usize, enc32_out: *mut u8, xyzt_out: *mut u64) -> Result<(), GpuError> {
+        check(ffi_short_msm::d377_msm_short_dev(ctx.0, dev, stream, xyzt, scalars, scalar_bytes, n, enc32_out, xyzt_out))
+    }
+    pub unsafe fn msm_short_encoded_resident(ctx: &GpuContext, dev: i32, stream: *mut c_void, enc32: *const u8, scalars: *const u8,
+                                             scalar_bytes: i32, n: usize, enc32_out: *mut u8, xyzt_out: *mut u64, status: *mut u8)
+        -> Result<(), GpuError> {
+        check(ffi_short_msm::d377_msm_short_encoded_dev(ctx.0, dev, stream, enc32, scalars, scalar_bytes, n, enc32_out, xyzt_out, status))
     }
 }
